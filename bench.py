@@ -1,10 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark: field-elements/sec of a 2^24-point forward NTT over BN254 Fr (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one forward transform of a whole 2^24-element vector (SURVEY §8d synthetic vector B,
-SplitMix64 limbs), resident in HBM when the timed region starts.
+SplitMix64 limbs), resident in HBM when the timed region starts.  The transform is in place, so step
+k + 1 transforms step k's output; the vector is filled again (same seed) just before the timed region,
+so the timed steps see the same inputs in every run with the same arguments.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds what
+takes work of its own after the timed region: the parity check, the secondary timings for N > 1 and
+the CPU baseline (each can still be left out with its ``--no-...`` option).
+
+``--dump-outputs DIR`` writes what the last timed step left in the caller's buffer (see dump_outputs).
 
 * N = 1: one MI355X, one 2^24 transform per step.
 * N > 1, one rank per GPU: by default ONE 2^24 transform split over the N ranks as the four-step
@@ -16,9 +24,10 @@ SplitMix64 limbs), resident in HBM when the timed region starts.
   before any GPU call), passes rank 0's line through and exits with the children's status; it
   refuses N above the visible device count (except the one-GPU rehearsal, NTT_BENCH_EXCHANGE=host).
   The line carries `rccl_ranks` (world size of the RCCL group), `exchange_ms` /
-  `exchange_gbps_per_link` (bytes each rank sends one peer per exchange / the all-to-all window) and
-  `parity`: after the timed region, the transform's output gathered to rank 0 is compared element by
-  element with a one-GPU plan there, plus the closed-form KAT of x_j = j at sampled k.
+  `exchange_gbps_per_link` (bytes each rank sends one peer per exchange / the all-to-all window) and,
+  with ``--full``, `parity`: after the timed region, the transform's output gathered to rank 0 is
+  compared element by element with a one-GPU plan there, plus the closed-form KAT of x_j = j at
+  sampled k.
 * ``--four-step`` at N = 1 times the partitioned schedule on one GPU (RCCL world size 1);
   ``--log-n 28 --four-step`` on 8 GPUs is BASELINE config 4.
 
@@ -31,7 +40,7 @@ Rank 0 prints one JSON line with
   inside the timed region);
 * `valu_roofline`: that launch against the v_mad_u64_u32 issue peak (the kernels are bound by
   256-bit multiply-adds, DESIGN.md §7);
-* `cpu_baseline`: the C oracle on the host (a bounded sample; see cpu_baseline()).
+* with ``--full``, `cpu_baseline`: the C oracle on the host (a bounded sample; see cpu_baseline()).
 """
 from __future__ import annotations
 
@@ -85,7 +94,12 @@ def parse():
     ap.add_argument("--field", type=int, default=1)
     ap.add_argument("--limbs", type=int, default=4)
     ap.add_argument("--inverse", action="store_true", help="time the inverse instead of the forward")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity check, the secondary timings (N > 1) and "
+                         "the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/<name>.npy (float64, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--four-step", "--dist", dest="four_step", action="store_true",
                     help="one transform split over all ranks (four-step + RCCL all-to-all); default for N > 1")
     ap.add_argument("--pieces", default=None,
@@ -97,10 +111,10 @@ def parse():
                          "arrives (default 1; 'auto')")
     ap.add_argument("--prewarm-s", type=float, default=0.3,
                     help="after --warmup, keep stepping (untimed) until the warmup lasted this long (clock ramp)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the post-timing parity check")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the post-timing parity check")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N > 1: skip the secondary timings after the headline (pipelined pieces, independent "
-                         "transforms per rank)")
+                    help="--full, N > 1: skip the secondary timings after the headline (pipelined pieces, "
+                         "independent transforms per rank)")
     ap.add_argument("--independent", action="store_true",
                     help="N > 1: one independent transform per rank (weak scaling, no data-path collective)")
     ap.add_argument("--cpu-log-n", type=int, default=22, help="C-oracle single-core sample size (log2)")
@@ -322,6 +336,37 @@ def _sample_ks(n: int):
     return sorted({0, 1, 2, n // 2, n - 1} | {rng.randrange(n) for _ in range(59)})
 
 
+DUMP_ROWS = 1 << 18  # elements written by --dump-outputs: 2^18 x 8 32-bit words x 8 B = 16 MiB at 4 limbs
+
+
+def dump_rows(count: int):
+    """Which elements of a `count`-element output --dump-outputs writes: all of them up to DUMP_ROWS,
+    else a fixed sample (seeded, sorted, without repeats), the same in every run."""
+    import numpy as np
+    if count <= DUMP_ROWS:
+        return np.arange(count, dtype=np.int64)
+    return np.sort(np.random.default_rng(20240229).choice(count, DUMP_ROWS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, name: str, data) -> dict:
+    """Write the transform's output `data` (int64 [count, limbs] or [count], little-endian 64-bit limbs)
+    as float64 arrays a build can be compared with another by:
+    * ``<name>.npy``       [rows, 2 limbs]: the sampled elements as 32-bit words, least significant first
+                           (every word is exact in float64; a 64-bit limb would not be);
+    * ``<name>_index.npy`` [rows]: which elements they are (dump_rows).
+    Returns {file name: shape}."""
+    import numpy as np
+    import torch
+    count = data.shape[0]
+    idx = dump_rows(count)
+    rows = data if len(idx) == count else data[torch.from_numpy(idx).to(data.device)]
+    words = np.ascontiguousarray(rows.cpu().numpy()).view(np.uint32).reshape(len(idx), -1).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}.npy"), words)
+    np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+    return {f"{name}.npy": list(words.shape), f"{name}_index.npy": [len(idx)]}
+
+
 def assemble_columns(parts, n1: int, c: int):
     """Column-layout shares -> the natural-order vector: rank g holds [n1][c] with element (k1, kc) =
     X[g c + kc + n2 k1] (n2 = G c), so [G][n1][c] transposed to [n1][G][c] is X in order."""
@@ -514,7 +559,10 @@ def main():
             # canonical vector, then the data is filled again
             eng.fill(data, "random", seed=2)
             tuned = eng.tune_pieces(data)
-        eng.fill(data, "random", seed=2)
+
+        def refill():
+            eng.fill(data, "random", seed=2)
+        refill()
         step = (lambda: eng.inverse(data)) if args.inverse else (lambda: eng.forward(data))
         plan_for_prof = eng
     else:
@@ -522,7 +570,10 @@ def main():
         from ntt_amd.ntt import NTTPlan
         plan = NTTPlan(field_id=args.field, log_n=args.log_n, limbs64=args.limbs, device=local)
         data = plan.empty()
-        plan.fill(data, "random", seed=2 + rank)  # each rank its own polynomial
+
+        def refill():
+            plan.fill(data, "random", seed=2 + rank)  # each rank its own polynomial
+        refill()
         step = (lambda: plan.inverse(data)) if args.inverse else (lambda: plan.forward(data))
         plan_for_prof = plan
 
@@ -554,6 +605,9 @@ def main():
 
     # ---- timed region: K steps bracketed by barrier + synchronize; per-launch HIP events recorded
     # on the launch stream between kernels (ntt_plan_set_profiling) accumulate per-launch times.
+    # The warmup ran a number of in-place steps that depends on the clock: start the timed steps from
+    # the seeded vector again, so that their inputs and outputs are the same in every run.
+    refill()
     plan_for_prof.set_profiling(True)
     barrier()
     torch.cuda.synchronize()
@@ -567,6 +621,10 @@ def main():
     launch_labels = plan_for_prof.last_launch_labels()  # which kernel each of those launches was
     plan_for_prof.set_profiling(False)
     exchange_ms = eng.exchange_ms() if four_step else None  # mean all-to-all window per step
+    # the caller's buffer as the last timed step left it (each rank its own share when N > 1)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, "output" if world == 1 else f"output_rank{rank}", data)
 
     elapsed = t1 - t0
     if use_dist:
@@ -686,8 +744,13 @@ def main():
                                     "unit": "T lane-MAD/s", "frac": ach / MAD_PEAK_T,
                                     "mads_per_launch": mads, "kernel": f"launch {k} of {len(launch_avg)}"}
     out["roofline"] = roof
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "files": dumped,
+                          "what": f"the caller's buffer after timed step {args.steps}: sampled elements as 32-bit "
+                                  "words in float64, and their indices"}
+    # ---- everything below is work of its own after the headline: only with --full
     # ---- parity, outside the timed region
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         if four_step:
             par = parity_four_step(args, eng, dist, rehearsal, local)
         else:
@@ -697,12 +760,12 @@ def main():
     # ---- secondary views for N > 1, outside the headline's timed region (same process group): the
     # pipelined exchange pieces (opt-in until they measurably win) and one independent transform per
     # rank (weak scaling, no data-path collective)
-    if four_step and world > 1 and not args.no_secondary:
+    if args.full and four_step and world > 1 and not args.no_secondary:
         args._tuned = tuned is not None
         sec = secondary_timings(args, eng, dist, rccl, local, barrier)
         if rank == 0:
             out["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.field, args.limbs if args.limbs != 1 else 1, args.cpu_log_n)
         except Exception as e:  # pragma: no cover

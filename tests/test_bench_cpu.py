@@ -115,6 +115,28 @@ def test_pmc_labels_from_kernel_names():
     assert launch_label("void ntt::k_build_tw<ntt::Eng29<9, 8, 0, 0> >(x)") == ""
 
 
+def test_dump_outputs_words_and_sample(tmp_path):
+    """--dump-outputs: 64-bit limbs leave as exact 32-bit words in float64 with the elements' indices;
+    a vector above DUMP_ROWS elements leaves as a fixed sample (sorted, no repeats, the same every call)."""
+    x = torch.tensor([[5, 0, 0, 0], [-1, 1, 0, 0], [1 << 62, 0, 0, -(1 << 63)]], dtype=torch.int64)
+    files = bench.dump_outputs(str(tmp_path), "output", x)
+    w = np.load(tmp_path / "output.npy")
+    assert w.dtype == np.float64 and w.shape == (3, 8) and files["output.npy"] == [3, 8]
+    assert w.tolist() == [[5, 0, 0, 0, 0, 0, 0, 0], [2 ** 32 - 1, 2 ** 32 - 1, 1, 0, 0, 0, 0, 0],
+                          [0, 2 ** 30, 0, 0, 0, 0, 0, 2 ** 31]]
+    assert np.load(tmp_path / "output_index.npy").tolist() == [0, 1, 2]
+    one = bench.dump_outputs(str(tmp_path), "p", torch.tensor([7, 469762048], dtype=torch.int64))
+    assert np.load(tmp_path / "p.npy").tolist() == [[7, 0], [469762048, 0]] and one["p_index.npy"] == [2]
+    n = 4 * bench.DUMP_ROWS
+    idx = bench.dump_rows(n)
+    assert len(idx) == bench.DUMP_ROWS and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(idx, bench.dump_rows(n))
+    big = torch.arange(n, dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path), "big", big)
+    assert np.array_equal(np.load(tmp_path / "big.npy")[:, 0], idx.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "big_index.npy"), idx.astype(np.float64))
+
+
 def test_device_probe_failure_is_reported(monkeypatch):
     """a failing device-count child is a reported failure, not '0 devices'."""
     import pytest

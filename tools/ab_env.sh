@@ -3,7 +3,7 @@
 # Run on the GPU box:  tools/ab_env.sh "NAME=VALUE ..." "NAME=VALUE ..." ...   ("" = defaults)
 # Output: one line per run, "<env> <ms_per_step> <launch_ms...>".
 set -o pipefail
-ARGS=${ARGS:---steps 100 --warmup 50 --no-cpu-baseline}
+ARGS=${ARGS:---full --steps 100 --warmup 50 --no-cpu-baseline}
 for rep in 1 2; do
   for envs in "$@"; do
     out=$(env $envs timeout -k 10 180 python3 bench.py $ARGS 2>/dev/null | tail -1) || { echo "[$envs] FAILED"; exit 1; }

@@ -3,7 +3,7 @@
 # twice to average out box drift.  Run on the GPU box:  tools/exp_variants.sh tag1 tag2 ...
 # Output: one line per run, "<tag> <ms_per_step> <launch_ms...>".
 set -o pipefail
-ARGS=${ARGS:---steps 100 --warmup 50 --no-cpu-baseline}
+ARGS=${ARGS:---full --steps 100 --warmup 50 --no-cpu-baseline}
 for rep in 1 2; do
   for tag in base "$@"; do
     if [ "$tag" = base ]; then lib=ntt_amd/libntt.so; else lib=ntt_amd/libntt_$tag.so; fi

@@ -9,7 +9,7 @@ O=${O:-gpurun_out/rehearse}
 mkdir -p $O
 for N in 2 4 8; do
   NTT_BENCH_EXCHANGE=host timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-    --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --steps 10 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --full --gpus $N --steps 10 --warmup 5 \
     > $O/bench_n$N.log 2>&1 || { echo "N=$N failed"; tail -20 $O/bench_n$N.log; exit 1; }
   grep '^{' $O/bench_n$N.log | tail -1
 done
