@@ -55,14 +55,20 @@ extern "C" {
 #define NTT_FIELD_P469762049 0   /* 7*2^26+1, generator 3 (GZKP-NTT.cu:7-8) */
 #define NTT_FIELD_BN254_FR 1     /* 0x30644e72...f0000001, generator 5 */
 #define NTT_FIELD_BLS12_381_FR 2 /* 0x73eda753...00000001, generator 7 */
+#define NTT_FIELD_GOLDILOCKS 3   /* 2^64 - 2^32 + 1 = 0xffffffff00000001, generator 7, two-adicity 32;
+                                  * 1 limb: 8-byte uint64_t elements */
 
 typedef struct ntt_plan ntt_plan;
 
 /* Create a plan for 2^log_n-point transforms on `device` (twiddle tables and scratch are cached in
  * the plan: the reference rebuilt its tables on every call, GZKP-NTT.cu:1476-1500).
- * limbs64: 1 (P469762049 only, `long long` elements), 4 (256-bit, cgbn_mem_t<256>), 6 (384-bit
- * template).  Replaces the table setup inside SSIP (GZKP-NTT.cu:1452-1505) and NTT_GZKP
- * (big-num.cu:278-309). */
+ * limbs64: 1 (P469762049, `long long` elements, and Goldilocks, `uint64_t` elements; Goldilocks takes
+ * no other limb count), 4 (256-bit, cgbn_mem_t<256>), 6 (384-bit template).  Replaces the table setup
+ * inside SSIP (GZKP-NTT.cu:1452-1505) and NTT_GZKP (big-num.cu:278-309).
+ * Goldilocks plans (the built-in field, or a custom 1-limb plan of that modulus) run every call of
+ * this header on canonical 8-byte elements, log_n 0..32.  Of the flags below they take
+ * NTT_PLAN_TWIDDLE_ONLY and ignore NTT_PLAN_SINGLE_LAUNCH; NTT_PLAN_MONTGOMERY_IO, NTT_PLAN_IN_PLACE
+ * and the rival schedules return NTT_ERR_ARG. */
 int ntt_plan_create(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs64, int device);
 
 /* Plan flags for the _ex constructors. */
@@ -174,7 +180,8 @@ int ntt_plan_create_ex(ntt_plan** out, int field_id, unsigned log_n, unsigned li
  * same ABI, `python -m ntt_amd.build --debug`) adds, from checks inside every pass kernel:
  *   0x100  an element index outside its buffer (the access went to element 0 instead)
  *   0x200  a caller input element >= p (the inputs must be canonical, as in the reference)
- *   0x400  an intermediate >= 2p (a lazy-reduction bound broke)
+ *   0x400  an intermediate >= 2p (a lazy-reduction bound broke; Goldilocks plans keep no lazy
+ *          values: an intermediate >= p)
  *   0x800  an output element >= p
  * The product build never sets these bits. */
 int ntt_plan_device_status(ntt_plan* plan, unsigned* bad);
@@ -185,9 +192,10 @@ int ntt_plan_set_watchdog(ntt_plan* plan, unsigned spins);
 
 /* Modulus-generic plan, like big-num.cu's `prime` / `omega` kernel arguments (big-num.cu:68,173,260):
  * modulus and generator given as limbs64 little-endian 64-bit limbs.  Accepted moduli: odd primes
- * with 2^log_n | p - 1 and, by limb count, p < 2^30 (1 limb: lazy values up to 4p must fit 32 bits,
- * so e.g. the 31-bit 2013265921 returns NTT_ERR_FIELD), p < 2^255 (4 limbs), p < 2^(29*14-6) with 2p
- * below 2^383 (6 limbs). */
+ * with 2^log_n | p - 1 and, by limb count, p < 2^30 or exactly the Goldilocks prime 0xffffffff00000001
+ * on 8-byte uint64_t elements (1 limb: lazy values up to 4p must fit 32 bits, so every other modulus
+ * >= 2^30, e.g. the 31-bit 2013265921, returns NTT_ERR_FIELD), p < 2^255 (4 limbs), p < 2^(29*14-6)
+ * with 2p below 2^383 (6 limbs). */
 int ntt_plan_create_custom(ntt_plan** out, const uint64_t* modulus, const uint64_t* generator, unsigned limbs64,
                            unsigned log_n, int device);
 

@@ -40,6 +40,7 @@ SOURCES += ["ntt_e256_rows.hip", "ntt_e256w_rows.hip", "ntt_ep_rows.hip"]  # bat
 SOURCES += [f"ntt_epi_{k}.hip" for k in ("col", "single", "fin", "misc")]  # P with 8-B scratch (NTT_PLAN_IN_PLACE)
 SOURCES += [f"ntt_e256wi_{k}.hip" for k in ("col", "single", "fin", "misc")]  # 48-B in place (NTT_PLAN_IN_PLACE)
 SOURCES += [f"ntt_e256t_{k}.hip" for k in ("col", "single", "fin", "misc")]  # 4096-element tiles (2^20 single transforms)
+SOURCES += [f"ntt_eg_{k}.hip" for k in ("col", "single", "fin", "misc", "rows")]  # Goldilocks, 8-B elements (Eng64G)
 SOURCES += ["ntt_plan.cpp", "ntt_rplan.cpp", "ntt_multi.cpp"]
 ARCH = os.environ.get("NTT_OFFLOAD_ARCH", "gfx950")
 

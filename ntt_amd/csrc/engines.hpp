@@ -6,10 +6,12 @@
 //                  class (BN254 Fr, BLS12-381 Fr, zero-padded P), L = 14 / W32 = 12 the 384-bit
 //                  (6 x 64-bit limb) template.
 //   Eng32<1>:      one 32-bit limb, HBM holds the reference's `long long` (P469762049 path).
+//   Eng64G:        the Goldilocks field, p = 2^64 - 2^32 + 1, one canonical 64-bit limb (field64.hpp).
 #pragma once
 #include "field.hpp"
 #include "field29.hpp"
 #include "field29_asm9.hpp"
+#include "field64.hpp"
 
 // Debug build (ntt_amd/libntt_debug.so, NTT_DEBUG_CHECKS=1): the pass kernels check every HBM index
 // against its buffer, the caller's inputs for canonical form, the lazy bound (< 2p) of every
@@ -61,6 +63,16 @@ __device__ __forceinline__ void ntt_dbg_flag(uint32_t* status, uint32_t bit) {
 #endif
 #ifndef NTT_TILE_LOG_256
 #define NTT_TILE_LOG_256 10
+#endif
+// Goldilocks engine (Eng64G): tile, elements per thread, pass-1 outer-twiddle table
+#ifndef NTT_TILE_LOG_G
+#define NTT_TILE_LOG_G 12
+#endif
+#ifndef NTT_EPT_G
+#define NTT_EPT_G 8
+#endif
+#ifndef NTT_G_PASS1_TABLE
+#define NTT_G_PASS1_TABLE 0
 #endif
 
 namespace ntt {
@@ -496,6 +508,117 @@ struct Eng32 {
     const uint32_t s = a[0] + b[0], d = a[0] - b[0] + A.p2;  // d < 4p: any 32-bit x is fine for Shoup
     a[0] = red(s, A.p2);
     b[0] = shoup(d, t.w[0], t.ws, A.p);
+  }
+};
+
+// ------------------------------------------------------------------------------ Goldilocks engine
+// p = 2^64 - 2^32 + 1 on 8-byte elements (field64.hpp).  p > 2^63 leaves no room for lazy values in
+// 64 bits, so every value is canonical between operations: in registers, LDS, scratch and tables.
+// An element is two 32-bit words (low, high) everywhere; a twiddle is the plain canonical value
+// (8 B per table entry), and the one product serves twiddles and variables alike (R_e = 1).
+//   * add / sub: one 64-bit add or subtract, the carry or borrow paid back with eps = 2^32 - 1;
+//   * mul: four v_mad_u64_u32, then lo - hh + hl eps (2^64 = eps, 2^96 = -1): no multiplication in
+//     the reduction, ~20 VALU ops per product.
+// The lazy bounds of the generic kernels (IN, MUL_OUT, the butterflies' K) are all 1 and `reduce`
+// does nothing.
+struct Eng64G {
+  static constexpr int W = 2;
+  static constexpr int MEMW = 2;
+  static constexpr int SCRW = 2;
+  static constexpr int TABW = 2;
+  static constexpr int TW = 2;
+  static constexpr int LDSW = 2;  // two 4-B planes: consecutive lanes hit consecutive banks
+  static constexpr int IN = 1;
+  static constexpr int MUL_OUT = 1;
+  static constexpr int EPT = NTT_EPT_G;
+  // 4096-element tiles (32 KiB LDS, 512 threads, two or more workgroups per CU) and >= 16 columns per
+  // column-pass workgroup: every HBM run is >= 128 B
+  static constexpr int TILE_LOG = NTT_TILE_LOG_G;
+  static constexpr int MIN_COLS_LOG = 4;
+  // pass 1 forms its outer twiddle from the L2-resident two-level tables (one more product per
+  // element) instead of streaming an n-entry table of 8-B entries beside the 8-B data
+  static constexpr bool PASS1_FULL_TABLE = NTT_G_PASS1_TABLE;
+  static constexpr bool NARROW_FIRST = true;  // HBM-bound like the P path: pass 1 reads wider runs
+  static constexpr bool SHOUP_OUTER = false;
+  static constexpr bool LDS_TW = false;
+  static constexpr int WAVES_PER_EU = 4;
+  static constexpr bool LDS_SPLIT = false;
+  static constexpr bool FASTRED = false;
+  struct Tw {
+    uint32_t w[2];  // canonical w (low, high)
+  };
+  struct Args {
+    Tw w8[3];       // w_8^1, w_8^2, w_8^3
+    Tw ninv;        // n^-1
+    uint32_t* dbg;  // debug builds: the plan's status word (NTT_DBG_*); null otherwise
+  };
+  __device__ static __forceinline__ uint64_t u64(const uint32_t (&x)[W]) { return ((uint64_t)x[1] << 32) | x[0]; }
+  __device__ static __forceinline__ void set(uint32_t (&x)[W], uint64_t v) {
+    x[0] = (uint32_t)v;
+    x[1] = (uint32_t)(v >> 32);
+  }
+  __device__ static bool dbg_canonical(const uint32_t (&x)[W], const Args&) { return gl64::is_canonical(u64(x)); }
+  template <int MW = MEMW>
+  __device__ static __forceinline__ void load(uint32_t (&x)[W], const uint32_t* __restrict__ base, size_t idx) {
+    static_assert(MW == 2, "HBM width");
+    const uint2 v = reinterpret_cast<const uint2*>(base)[idx];
+    x[0] = v.x;
+    x[1] = v.y;
+  }
+  template <int FROM, int TO, bool FAST = false, bool R32 = true>
+  __device__ static __forceinline__ void reduce(uint32_t (&)[W], const Args&) {}  // always canonical
+  template <int MW = MEMW, bool WT = false>
+  __device__ static __forceinline__ void put(uint32_t* __restrict__ base, size_t idx, const uint32_t (&x)[W]) {
+    static_assert(MW == 2 && !WT, "HBM width; write-through stores: Eng29 engines only");
+    reinterpret_cast<uint2*>(base)[idx] = make_uint2(x[0], x[1]);
+  }
+  // scratch between passes: canonical like everything else (the "lazy" check of the debug build
+  // degenerates to the canonical one)
+  template <int BOUND, bool FAST = false, int MW = MEMW, bool WT = false>
+  __device__ static __forceinline__ void store_lazy(uint32_t* __restrict__ base, size_t idx, uint32_t (&x)[W],
+                                                    [[maybe_unused]] const Args& A) {
+#if NTT_DEBUG_CHECKS
+    if (!gl64::is_canonical(u64(x))) ntt_dbg_flag(A.dbg, NTT_DBG_LAZY);
+#endif
+    put<MW, WT>(base, idx, x);
+  }
+  template <int BOUND, bool FAST = false, int MW = MEMW>
+  __device__ static __forceinline__ void store(uint32_t* __restrict__ base, size_t idx, uint32_t (&x)[W],
+                                               [[maybe_unused]] const Args& A) {
+#if NTT_DEBUG_CHECKS
+    if (!gl64::is_canonical(u64(x))) ntt_dbg_flag(A.dbg, NTT_DBG_OUTPUT);
+#endif
+    put<MW>(base, idx, x);
+  }
+  __device__ static __forceinline__ void tload(Tw& t, const uint32_t* __restrict__ tab, size_t idx) {
+    const uint2 v = reinterpret_cast<const uint2*>(tab)[idx];
+    t.w[0] = v.x;
+    t.w[1] = v.y;
+  }
+  __device__ static __forceinline__ void tload_lds(Tw& t, const uint32_t* lds_tw, uint32_t idx) {
+    const uint2 v = reinterpret_cast<const uint2*>(lds_tw)[idx];
+    t.w[0] = v.x;
+    t.w[1] = v.y;
+  }
+  __device__ static __forceinline__ void mul(uint32_t (&x)[W], const Tw& t, const Args&) {
+    set(x, gl64::mul(u64(x), u64(t.w)));
+  }
+  __device__ static __forceinline__ void mul_u(uint32_t (&x)[W], const Tw& t, const Args& A) { mul(x, t, A); }
+  __device__ static __forceinline__ void mulv(uint32_t (&x)[W], const uint32_t (&y)[W], const Args&) {
+    set(x, gl64::mul(u64(x), u64(y)));
+  }
+  // DIF butterfly on canonical values: (a + b, a - b)
+  template <int K>
+  __device__ static __forceinline__ void bfly_l(uint32_t (&a)[W], uint32_t (&b)[W], const Args&) {
+    const uint64_t x = u64(a), y = u64(b);
+    set(a, gl64::add(x, y));
+    set(b, gl64::sub(x, y));
+  }
+  template <int K>
+  __device__ static __forceinline__ void bfly_w_l(uint32_t (&a)[W], uint32_t (&b)[W], const Tw& t, const Args&) {
+    const uint64_t x = u64(a), y = u64(b);
+    set(a, gl64::add(x, y));
+    set(b, gl64::mul(gl64::sub(x, y), u64(t.w)));
   }
 };
 

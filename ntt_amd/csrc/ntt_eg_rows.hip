@@ -1,0 +1,5 @@
+// Eng64G (Goldilocks, 8-B elements): k_pass instantiations for KIND_ROWS (several single-tile transforms per workgroup).
+#include "ntt_kernels_impl.hpp"
+namespace ntt {
+NTT_INSTANTIATE_KIND(Eng64G, KIND_ROWS)
+}  // namespace ntt

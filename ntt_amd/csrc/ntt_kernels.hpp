@@ -32,9 +32,11 @@ constexpr int kRowsMinLog = 3;
 // the largest KIND_ROWS radix of an engine, measured (profiles/r05_rows/): 2^7 on the
 // 256-bit engines (1024-element tiles, 256-thread workgroups); 2^6 on P, whose 8192-element tiles
 // make 1024-thread workgroups that lose to one transform per workgroup from 2^7 up (+20 %, 2^8 +180 %)
+// (Goldilocks, W = 2: 4096-element tiles and 512-thread workgroups, the P path's shape; its limit is
+// taken from P, not measured)
 template <class E>
 constexpr int rows_max_log() {
-  return E::W == 1 ? 6 : 7;
+  return E::W <= 2 ? 6 : 7;
 }
 
 // Elements per workgroup tile of the multi-pass kernels (engines.hpp: E::TILE_LOG, E::EPT per thread).
@@ -70,6 +72,10 @@ struct HasRows<Eng256w> {  // the 6 x 64-bit layout of 256-bit moduli (BLS12-381
 };
 template <>
 struct HasRows<EngP> {  // P469762049 (the reference's own field), ntt_ep_rows.hip
+  static constexpr bool value = true;
+};
+template <>
+struct HasRows<Eng64G> {  // Goldilocks, ntt_eg_rows.hip
   static constexpr bool value = true;
 };
 

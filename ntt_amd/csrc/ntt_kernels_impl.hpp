@@ -2035,7 +2035,7 @@ __global__ void k_fill_random(uint32_t* __restrict__ dst, size_t n, uint64_t see
     const uint64_t j = fill_index(i, fm);
     if constexpr (MEMW == 2) {
       const uint64_t v = splitmix64((seed << 32) + 4 * j) & ((1ull << top_bits) - 1);
-      reinterpret_cast<uint2*>(dst)[i] = make_uint2((uint32_t)v, 0u);
+      reinterpret_cast<uint2*>(dst)[i] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));  // P: top_bits < 32
     } else {
       uint32_t v[MEMW];
 #pragma unroll

@@ -340,7 +340,29 @@ static bool schedule(unsigned log_n, unsigned tile_log, unsigned min_cols_log, b
     }
   }
   if (!schedule_ok(r, p, tile_log)) std::sort(r, r + p);
-  return schedule_ok(r, p, tile_log);
+  if (schedule_ok(r, p, tile_log)) return true;
+  // Neither split passes (4096-element tiles with radices <= 2^8 at 2^17: 5+6+6 has r_1 + r_p = 11):
+  // the ascending sequence of p radices in [3, rmax] that does, with the smallest largest radix, then
+  // the largest smallest one (2^17: 5+5+7).
+  unsigned best[8] = {0}, v[8] = {0}, bmax = 99, bmin = 0;
+  for (unsigned i = 0; i < p; ++i) v[i] = 3;
+  for (;;) {
+    unsigned sum = 0;
+    for (unsigned i = 0; i < p; ++i) sum += v[i];
+    if (sum == log_n && schedule_ok(v, p, tile_log) && (v[p - 1] < bmax || (v[p - 1] == bmax && v[0] > bmin))) {
+      bmax = v[p - 1];
+      bmin = v[0];
+      for (unsigned i = 0; i < p; ++i) best[i] = v[i];
+    }
+    int k = (int)p - 1;  // next non-decreasing sequence
+    while (k >= 0 && v[k] == rmax) --k;
+    if (k < 0) break;
+    ++v[k];
+    for (unsigned i = k + 1; i < p; ++i) v[i] = v[k];
+  }
+  if (bmax == 99) return false;
+  for (unsigned i = 0; i < p; ++i) r[i] = best[i];
+  return true;
 }
 
 // NTT_PLAN_IN_PLACE: a palindromic sequence (r_i = r_{p-1-i}, 3 <= r_i <= rmax, schedule_ok) with the
@@ -512,6 +534,30 @@ struct EngHost<Eng32<N, MEMW_, SCR_>> {
     };
     for (int k = 0; k < 3; ++k) tw(w8[k], A.w8[k]);
     tw(ninv, A.ninv);
+  }
+};
+
+// Goldilocks: the host works on the modulus zero-padded to three 32-bit words (the no-carry host
+// Montgomery product needs a top word below 2^31 - 1, and p's own top word is 2^32 - 1); the engine's
+// values and table entries are the canonical low two words, and its radix R_e is 1.
+constexpr uint64_t kGoldilocksP = 0xFFFFFFFF00000001ull;
+template <>
+struct EngHost<Eng64G> {
+  static constexpr int NH = 3;
+  using EA = Eng64G::Args;
+  HostField<NH> const* H = nullptr;
+  void init(const HostField<NH>& h) { H = &h; }
+  void encode(const Vec<NH>& c, uint32_t* out) const {
+    out[0] = c[0];
+    out[1] = c[1];
+  }
+  void encode_scaled(const Vec<NH>& c, uint32_t* out) const { encode(c, out); }
+  bool check_modulus(const uint32_t* p) const {
+    return p[0] == (uint32_t)kGoldilocksP && p[1] == (uint32_t)(kGoldilocksP >> 32) && p[2] == 0u;
+  }
+  void fill_args(EA& A, const uint32_t*, const Vec<NH>* w8, const Vec<NH>& ninv) const {
+    for (int k = 0; k < 3; ++k) encode(w8[k], A.w8[k].w);
+    encode(ninv, A.ninv.w);
   }
 };
 
@@ -1167,10 +1213,11 @@ struct PlanImpl final : PlanBase {
   int coset(void* d, const uint64_t* shift, unsigned limbs64, bool inverse, hipStream_t st) override {
     if (!d || !shift || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
     Vec<NH> c{};
-    for (int i = 0; i < NH; ++i) c[i] = (uint32_t)(shift[i / 2] >> (32 * (i % 2)));
+    // (the host words may reach past the caller's limbs: Goldilocks, NH = 3 over one 64-bit limb)
+    for (int i = 0; i < NH && (unsigned)(i / 2) < limbs64; ++i) c[i] = (uint32_t)(shift[i / 2] >> (32 * (i % 2)));
     for (unsigned i = (NH + 1) / 2; i < limbs64; ++i)
       if (shift[i]) return NTT_ERR_ARG;
-    if ((NH & 1) && (shift[NH / 2] >> 32)) return NTT_ERR_ARG;
+    if ((NH & 1) && (unsigned)(NH / 2) < limbs64 && (shift[NH / 2] >> 32)) return NTT_ERR_ARG;
     Vec<NH> pv;
     for (int i = 0; i < NH; ++i) pv[i] = H.M.p[i];
     if (!vec_lt<NH>(c, pv) || c == Vec<NH>{}) return NTT_ERR_ARG;
@@ -1242,6 +1289,10 @@ struct PlanImpl final : PlanBase {
   Vec<NH> engine_radix_mod_p() const {
     if constexpr (IsEng32<E>::value) {
       return H.r1;  // 2^(32N) mod p
+    } else if constexpr (std::is_same_v<E, Eng64G>) {
+      Vec<NH> one{};  // plain canonical values: no radix
+      one[0] = 1;
+      return one;
     } else {
       return EH.kR;  // 2^(29L) mod p
     }
@@ -1978,10 +2029,11 @@ struct FieldDef {
   uint64_t p[4];
   uint64_t g;
 };
-static const FieldDef kFields[3] = {
+static const FieldDef kFields[4] = {
     {{469762049ull, 0, 0, 0}, 3},
     {{0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}, 5},
     {{0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull}, 7},
+    {{kGoldilocksP, 0, 0, 0}, 7},
 };
 
 static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const uint64_t* g64, unsigned limbs64,
@@ -1992,6 +2044,9 @@ static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const 
   if (rivals & (rivals - 1)) return NTT_ERR_ARG;  // one rival schedule per plan
   if ((flags & NTT_PLAN_IN_PLACE) && (rivals || (flags & NTT_PLAN_TWIDDLE_ONLY)))
     return NTT_ERR_ARG;
+  // Goldilocks (8-B elements, Eng64G): the default schedule only
+  const bool goldilocks = limbs64 == 1 && p64[0] == kGoldilocksP;
+  if (goldilocks && (rivals || (flags & (NTT_PLAN_IN_PLACE | NTT_PLAN_MONTGOMERY_IO)))) return NTT_ERR_ARG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return NTT_ERR_NODEV;
   if (device < 0 || device >= ndev) return NTT_ERR_ARG;
@@ -2003,7 +2058,11 @@ static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const 
     g32[2 * i + 1] = (uint32_t)(g64[i] >> 32);
   }
   int rc;
-  if (limbs64 == 1) {
+  if (goldilocks) {
+    auto impl = std::make_unique<PlanImpl<Eng64G>>();
+    rc = impl->init(p32, g32, log_n, device, flags);
+    out = std::move(impl);
+  } else if (limbs64 == 1) {
     if (p64[0] >= (1ull << 31)) return NTT_ERR_FIELD;  // `long long` path: 31-bit primes
     if (flags & NTT_PLAN_IN_PLACE) {  // in place needs 8-B scratch elements (the caller's layout)
       auto impl = std::make_unique<PlanImpl<EngPI>>();
@@ -2179,9 +2238,10 @@ int ntt_plan_create(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs
 
 static int create_field_plan(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs64, int device,
                              unsigned flags, bool allow_wide) {
-  if (field_id < 0 || field_id > 2) return set_err(NTT_ERR_ARG);
+  if (field_id < 0 || field_id > 3) return set_err(NTT_ERR_ARG);
   if (limbs64 != 1 && limbs64 != 4 && limbs64 != 6) return set_err(NTT_ERR_ARG);
-  if (limbs64 == 1 && field_id != NTT_FIELD_P469762049) return set_err(NTT_ERR_ARG);
+  if (limbs64 == 1 && field_id != NTT_FIELD_P469762049 && field_id != NTT_FIELD_GOLDILOCKS) return set_err(NTT_ERR_ARG);
+  if (field_id == NTT_FIELD_GOLDILOCKS && limbs64 != 1) return set_err(NTT_ERR_ARG);  // 8-byte elements only
   const FieldDef& F = kFields[field_id];
   uint64_t p[6] = {0}, g[6] = {0};
   for (unsigned i = 0; i < limbs64 && i < 4; ++i) p[i] = F.p[i];

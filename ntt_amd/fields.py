@@ -4,11 +4,13 @@ from __future__ import annotations
 P469762049 = 469762049  # 7 * 2^26 + 1, generator 3 (reference GZKP-NTT.cu:7-8)
 BN254_FR = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 BLS12_381_FR = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+GOLDILOCKS = 0xFFFFFFFF00000001  # 2^64 - 2^32 + 1, generator 7, two-adicity 32 (8-byte elements, 1 limb)
 
 FIELDS = {
     0: ("P469762049", P469762049, 3),
     1: ("BN254_FR", BN254_FR, 5),
     2: ("BLS12_381_FR", BLS12_381_FR, 7),
+    3: ("GOLDILOCKS", GOLDILOCKS, 7),
 }
 
 

@@ -18,6 +18,7 @@ NTT_ERR_ARG, NTT_ERR_HIP, NTT_ERR_RCCL, NTT_ERR_FIELD, NTT_ERR_NODEV, NTT_ERR_DE
 NTT_FIELD_P469762049 = 0
 NTT_FIELD_BN254_FR = 1
 NTT_FIELD_BLS12_381_FR = 2
+NTT_FIELD_GOLDILOCKS = 3
 NTT_PLAN_TWIDDLE_ONLY = 1
 NTT_PLAN_MONTGOMERY_IO = 2
 NTT_PLAN_STOCKHAM = 4

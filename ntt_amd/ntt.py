@@ -41,24 +41,23 @@ def int_to_limbs(v: int, limbs64: int) -> List[int]:
     return [(v >> (64 * i)) & ((1 << 64) - 1) for i in range(limbs64)]
 
 
-def to_device(values: Iterable[int], limbs64: int, device="cuda") -> torch.Tensor:
-    """Python ints -> device tensor in the cgbn_mem_t layout (int64 [n, limbs64]; [n] for 1 limb)."""
+def host_array(values: Iterable[int], limbs64: int) -> np.ndarray:
+    """Python ints -> host array in the cgbn_mem_t layout: int64 bit patterns, [n, limbs64] ([n] for
+    1 limb).  One-limb values go through uint64, so elements >= 2^63 (Goldilocks) keep their bits."""
     vals = list(values)
     if limbs64 == 1:
-        host = np.array(vals, dtype=np.int64)
-        return torch.from_numpy(host).to(device)
+        return np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64).view(np.int64)
     host = np.zeros((len(vals), limbs64), dtype=np.uint64)
     for j, v in enumerate(vals):
         for i in range(limbs64):
             host[j, i] = (v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF
-    return torch.from_numpy(host.view(np.int64)).to(device)
+    return host.view(np.int64)
 
 
-def from_device(t: torch.Tensor) -> List[int]:
-    """Device tensor (cgbn_mem_t layout) -> Python ints."""
-    host = t.detach().cpu().numpy()
+def host_ints(host: np.ndarray) -> List[int]:
+    """Host array in the cgbn_mem_t layout (host_array) -> Python ints (unsigned)."""
     if host.ndim == 1:
-        return [int(v) for v in host]
+        return [int(v) for v in host.view(np.uint64)]
     u = host.view(np.uint64)
     out = []
     for row in u:
@@ -69,6 +68,16 @@ def from_device(t: torch.Tensor) -> List[int]:
     return out
 
 
+def to_device(values: Iterable[int], limbs64: int, device="cuda") -> torch.Tensor:
+    """Python ints -> device tensor in the cgbn_mem_t layout (int64 [n, limbs64]; [n] for 1 limb)."""
+    return torch.from_numpy(host_array(values, limbs64)).to(device)
+
+
+def from_device(t: torch.Tensor) -> List[int]:
+    """Device tensor (cgbn_mem_t layout) -> Python ints."""
+    return host_ints(t.detach().cpu().numpy())
+
+
 BEALTO_FLAGS = {"bellperson": _L.NTT_PLAN_BELLPERSON, "v1": _L.NTT_PLAN_IMPROVED_V1, "v2": _L.NTT_PLAN_IMPROVED_V2,
                 "v3": _L.NTT_PLAN_IMPROVED_V3, "v4": _L.NTT_PLAN_IMPROVED_V4}
 
@@ -76,7 +85,8 @@ BEALTO_FLAGS = {"bellperson": _L.NTT_PLAN_BELLPERSON, "v1": _L.NTT_PLAN_IMPROVED
 class NTTPlan:
     """A cached transform plan: twiddle tables and scratch live on the device.
 
-    ``field_id`` selects a built-in field (0 P469762049, 1 BN254 Fr, 2 BLS12-381 Fr); or pass
+    ``field_id`` selects a built-in field (0 P469762049, 1 BN254 Fr, 2 BLS12-381 Fr, 3 Goldilocks
+    with ``limbs64=1``: int64 bit patterns of uint64 elements); or pass
     ``modulus``/``generator`` ints for any odd prime below 2^(64*limbs64 - 1) with 2^log_n | p - 1
     (big-num.cu's modulus-generic path).
     """

@@ -1,0 +1,32 @@
+"""The Goldilocks arithmetic of ntt_amd/csrc/field64.hpp (the text the Eng64G kernels run) checked on
+the host: tests/c/field64_check.cpp compares add, sub, mul and canonicalisation with unsigned
+__int128 arithmetic mod p on the edge set's cross product, the non-canonical patterns and 10^6
+seeded random pairs."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _host_compiler():
+    for cand in (os.environ.get("CXX"), "g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++"):
+        if cand and (shutil.which(cand) or os.path.exists(cand)):
+            return cand
+    return None
+
+
+def test_field64_matches_int128_arithmetic(tmp_path):
+    cxx = _host_compiler()
+    if cxx is None:
+        pytest.fail("no host C++ compiler found (g++, c++, clang++)")
+    exe = str(tmp_path / "field64_check")
+    cmd = [cxx, "-O2", "-std=c++17", "-I", os.path.join(ROOT, "ntt_amd", "csrc"),
+           os.path.join(ROOT, "tests", "c", "field64_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    assert "field64_check: ok" in r.stdout
