@@ -57,6 +57,10 @@ extern "C" {
 #define NTT_FIELD_BLS12_381_FR 2 /* 0x73eda753...00000001, generator 7 */
 #define NTT_FIELD_GOLDILOCKS 3   /* 2^64 - 2^32 + 1 = 0xffffffff00000001, generator 7, two-adicity 32;
                                   * 1 limb: 8-byte uint64_t elements */
+#define NTT_FIELD_BABYBEAR 4     /* 2^31 - 2^27 + 1 = 0x78000001, generator 31, two-adicity 27;
+                                  * 1 limb: 4-byte uint32_t elements */
+#define NTT_FIELD_KOALABEAR 5    /* 2^31 - 2^24 + 1 = 0x7f000001, generator 3, two-adicity 24;
+                                  * 1 limb: 4-byte uint32_t elements */
 
 typedef struct ntt_plan ntt_plan;
 
@@ -68,12 +72,20 @@ typedef struct ntt_plan ntt_plan;
  * Goldilocks plans (the built-in field, or a custom 1-limb plan of that modulus) run every call of
  * this header on canonical 8-byte elements, log_n 0..32.  Of the flags below they take
  * NTT_PLAN_TWIDDLE_ONLY and ignore NTT_PLAN_SINGLE_LAUNCH; NTT_PLAN_MONTGOMERY_IO, NTT_PLAN_IN_PLACE
- * and the rival schedules return NTT_ERR_ARG. */
+ * and the rival schedules return NTT_ERR_ARG.
+ * BabyBear and KoalaBear plans (and NTT_PLAN_ELEM32 custom plans) run every call of this header on
+ * canonical 4-byte uint32_t elements, limbs64 = 1 only (any other count: NTT_ERR_ARG), log_n up to the
+ * field's two-adicity (27 / 24; above it NTT_ERR_FIELD); ntt_plan_info reports elem_bytes 4.  A coset
+ * shift is still one uint64_t holding a value below p.  They take NTT_PLAN_TWIDDLE_ONLY and
+ * NTT_PLAN_MONTGOMERY_IO (with R = 2^32), ignore NTT_PLAN_SINGLE_LAUNCH, and return NTT_ERR_ARG for
+ * NTT_PLAN_IN_PLACE and the rival schedules.  ntt_rplan_create accepts them; ntt_mplan_create returns
+ * NTT_ERR_ARG (its exchange sizes count 8-byte words). */
 int ntt_plan_create(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs64, int device);
 
 /* Plan flags for the _ex constructors. */
 #define NTT_PLAN_TWIDDLE_ONLY 1u /* only the w_n tables: fill / twiddle_pack / transpose, no transforms */
-/* Elements are in Montgomery form x R mod p, R = 2^(64 limbs64) (CGBN's bn2mont domain,
+/* Elements are in Montgomery form x R mod p, R = 2^(64 limbs64) -- R = 2^32 on the 4-byte elements of
+ * NTT_PLAN_ELEM32 plans, the form Plonky3 and RISC Zero keep BabyBear in -- (CGBN's bn2mont domain,
  * impl_cuda.cu:980-1010; the form arkworks / sppark / ICICLE callers keep their data in).  The
  * transforms are linear, so forward / inverse / coset are unchanged (NTT(x R) = NTT(x) R); the
  * pointwise product becomes the Montgomery product a b R^-1 so that polymul maps (a R, b R) to
@@ -171,6 +183,13 @@ int ntt_plan_create(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs
 #define NTT_PLAN_IMPROVED_V2 1024u
 #define NTT_PLAN_IMPROVED_V3 2048u
 #define NTT_PLAN_IMPROVED_V4 4096u
+/* 4-byte elements: with ntt_plan_create_custom_ex and limbs64 = 1, a plan for any odd prime p < 2^31
+ * with 2^log_n | p - 1 on canonical uint32_t elements (the 31-bit engine: values canonical between all
+ * operations, so p may exceed 2^30).  Any other limb count returns NTT_ERR_ARG, a modulus >= 2^31
+ * (Goldilocks included) NTT_ERR_FIELD.  Implied (and accepted) on NTT_FIELD_BABYBEAR and
+ * NTT_FIELD_KOALABEAR; NTT_ERR_ARG on fields 0-3.  Without the flag nothing changes: a 1-limb custom
+ * plan of a modulus >= 2^30 other than Goldilocks still returns NTT_ERR_FIELD. */
+#define NTT_PLAN_ELEM32 8192u
 int ntt_plan_create_ex(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs64, int device, unsigned flags);
 /* Device-side status of a plan (blocking: synchronises the device, then reads and clears it).
  * *bad bit 0: an inter-workgroup wait gave up at its watchdog (NTT_PLAN_SINGLE_LAUNCH, or the fused
@@ -180,8 +199,8 @@ int ntt_plan_create_ex(ntt_plan** out, int field_id, unsigned log_n, unsigned li
  * same ABI, `python -m ntt_amd.build --debug`) adds, from checks inside every pass kernel:
  *   0x100  an element index outside its buffer (the access went to element 0 instead)
  *   0x200  a caller input element >= p (the inputs must be canonical, as in the reference)
- *   0x400  an intermediate >= 2p (a lazy-reduction bound broke; Goldilocks plans keep no lazy
- *          values: an intermediate >= p)
+ *   0x400  an intermediate >= 2p (a lazy-reduction bound broke; Goldilocks and 4-byte-element plans
+ *          keep no lazy values: an intermediate >= p)
  *   0x800  an output element >= p
  * The product build never sets these bits. */
 int ntt_plan_device_status(ntt_plan* plan, unsigned* bad);
@@ -194,8 +213,8 @@ int ntt_plan_set_watchdog(ntt_plan* plan, unsigned spins);
  * modulus and generator given as limbs64 little-endian 64-bit limbs.  Accepted moduli: odd primes
  * with 2^log_n | p - 1 and, by limb count, p < 2^30 or exactly the Goldilocks prime 0xffffffff00000001
  * on 8-byte uint64_t elements (1 limb: lazy values up to 4p must fit 32 bits, so every other modulus
- * >= 2^30, e.g. the 31-bit 2013265921, returns NTT_ERR_FIELD), p < 2^255 (4 limbs), p < 2^(29*14-6)
- * with 2p below 2^383 (6 limbs). */
+ * >= 2^30, e.g. the 31-bit 2013265921, returns NTT_ERR_FIELD; with NTT_PLAN_ELEM32 any p < 2^31 on
+ * 4-byte uint32_t elements), p < 2^255 (4 limbs), p < 2^(29*14-6) with 2p below 2^383 (6 limbs). */
 int ntt_plan_create_custom(ntt_plan** out, const uint64_t* modulus, const uint64_t* generator, unsigned limbs64,
                            unsigned log_n, int device);
 
@@ -394,7 +413,9 @@ int ntt_rplan_destroy(ntt_rplan* rp);
  * the most balanced split (2^24 on the 256-bit engines: n1 = 2^16, n2 = 2^8):
  *   forward input  (row layout):    d_data[g] = [r][n2], element (a, j2) = x[g r + a + n1 j2]
  *   forward output (column layout): d_data[g] = [n1][c], element (k1, kc) = X[g c + kc + n2 k1]
- * The inverse takes the column layout back to the row layout (1/n included).  Asynchronous. */
+ * The inverse takes the column layout back to the row layout (1/n included).  Asynchronous.
+ * NTT_FIELD_BABYBEAR and NTT_FIELD_KOALABEAR (4-byte elements) return NTT_ERR_ARG: the exchange
+ * sizes count 8-byte words. */
 typedef struct ntt_mplan ntt_mplan;
 int ntt_mplan_create(ntt_mplan** out, int field_id, unsigned log_n, unsigned limbs64, int ngpus, const int* devices);
 int ntt_forward_multi(ntt_mplan* plan, void* const* d_data, void* const* hip_streams);

@@ -41,6 +41,7 @@ SOURCES += [f"ntt_epi_{k}.hip" for k in ("col", "single", "fin", "misc")]  # P w
 SOURCES += [f"ntt_e256wi_{k}.hip" for k in ("col", "single", "fin", "misc")]  # 48-B in place (NTT_PLAN_IN_PLACE)
 SOURCES += [f"ntt_e256t_{k}.hip" for k in ("col", "single", "fin", "misc")]  # 4096-element tiles (2^20 single transforms)
 SOURCES += [f"ntt_eg_{k}.hip" for k in ("col", "single", "fin", "misc", "rows")]  # Goldilocks, 8-B elements (Eng64G)
+SOURCES += [f"ntt_e31_{k}.hip" for k in ("col", "single", "fin", "misc", "rows")]  # primes < 2^31, 4-B elements (Eng31)
 SOURCES += ["ntt_plan.cpp", "ntt_rplan.cpp", "ntt_multi.cpp"]
 ARCH = os.environ.get("NTT_OFFLOAD_ARCH", "gfx950")
 

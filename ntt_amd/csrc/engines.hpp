@@ -7,10 +7,12 @@
 //                  (6 x 64-bit limb) template.
 //   Eng32<1>:      one 32-bit limb, HBM holds the reference's `long long` (P469762049 path).
 //   Eng64G:        the Goldilocks field, p = 2^64 - 2^32 + 1, one canonical 64-bit limb (field64.hpp).
+//   Eng31:         any odd prime p < 2^31 (BabyBear, KoalaBear) on canonical 4-byte elements (field31.hpp).
 #pragma once
 #include "field.hpp"
 #include "field29.hpp"
 #include "field29_asm9.hpp"
+#include "field31.hpp"
 #include "field64.hpp"
 
 // Debug build (ntt_amd/libntt_debug.so, NTT_DEBUG_CHECKS=1): the pass kernels check every HBM index
@@ -73,6 +75,22 @@ __device__ __forceinline__ void ntt_dbg_flag(uint32_t* status, uint32_t bit) {
 #endif
 #ifndef NTT_G_PASS1_TABLE
 #define NTT_G_PASS1_TABLE 0
+#endif
+// 31-bit engine (Eng31): tile, elements per thread, narrowest column group, pass-1 outer-twiddle table
+#ifndef NTT_TILE_LOG_31
+#define NTT_TILE_LOG_31 13
+#endif
+#ifndef NTT_EPT_31
+#define NTT_EPT_31 8
+#endif
+#ifndef NTT_MIN_COLS_LOG_31
+#define NTT_MIN_COLS_LOG_31 4
+#endif
+#ifndef NTT_PREF_COLS_LOG_31
+#define NTT_PREF_COLS_LOG_31 5
+#endif
+#ifndef NTT_31_PASS1_TABLE
+#define NTT_31_PASS1_TABLE 1
 #endif
 
 namespace ntt {
@@ -619,6 +637,119 @@ struct Eng64G {
     const uint64_t x = u64(a), y = u64(b);
     set(a, gl64::add(x, y));
     set(b, gl64::mul(gl64::sub(x, y), u64(t.w)));
+  }
+};
+
+// ------------------------------------------------------------------------------ 31-bit engine
+// Any odd prime p < 2^31 on 4-byte elements (field31.hpp): BabyBear, KoalaBear, and NTT_PLAN_ELEM32
+// custom plans.  2p no longer leaves room for a second lazy value in 32 bits, so every value is
+// canonical between operations: in registers, LDS, scratch and tables (IN = MUL_OUT = 1, `reduce`
+// does nothing).  One word per element everywhere: the caller's buffers, the scratch, the
+// element-format tables (w 2^32 mod p) and LDS; twiddle tables hold Shoup pairs (w, floor(w 2^32 / p)).
+//   * add / sub: one add or subtract and one min (v_min_u32 against the value shifted by p);
+//   * twiddle product: Shoup's, 4 VALU ops, then one min;
+//   * variable product: Montgomery with R = 2^32, 6 ops, then one min;
+//   * the twiddled butterfly feeds a - b + p (< 2p: any 32-bit value is a valid Shoup input) to the
+//     product unreduced: 2 + 4 + 2 ops for its second output.
+// Shape: the P path's (8192-element tiles, 8 elements per thread, 1024 threads, 4 waves per SIMD, the
+// pass's w_R^e table staged in LDS, pass 1 a radix narrower).  DESIGN section 7 has the measurements.
+struct Eng31 {
+  static constexpr int W = 1;
+  static constexpr int MEMW = 1;
+  static constexpr int SCRW = 1;
+  static constexpr int TABW = 1;
+  static constexpr int TW = 2;  // Shoup pair (w, floor(w 2^32 / p))
+  static constexpr int LDSW = 1;
+  static constexpr int IN = 1;
+  static constexpr int MUL_OUT = 1;
+  static constexpr int EPT = NTT_EPT_31;
+  static constexpr int TILE_LOG = NTT_TILE_LOG_31;
+  // 2^4 columns of 4 B are 64-B runs; 2^5 (128-B runs) caps the radix at 2^8, which leaves 2^17
+  // without a valid radix sequence on 8192-element tiles (r_1 + r_p >= 13 and r_{p-1} + r_p >= 13 need
+  // 18 bits in three passes, and two passes stop at 16)
+  static constexpr int MIN_COLS_LOG = NTT_MIN_COLS_LOG_31;
+  // ... so the kernels are instantiated down to 2^4 columns (radix 2^9) and the planner prefers 2^5
+  // (radices <= 2^8) wherever that costs no extra pass: 2^16 runs 8 + 8 instead of 7 + 9 (measured 15 %
+  // faster in a batch of 64) and 2^24 8 + 8 + 8 instead of 7 + 8 + 9 (within 2 %);
+  // 2^17 and 2^18 keep 8 + 9 and 9 + 9 (ntt_plan.cpp schedule_for)
+  static constexpr int PREF_COLS_LOG = NTT_PREF_COLS_LOG_31 > NTT_MIN_COLS_LOG_31 ? NTT_PREF_COLS_LOG_31 : NTT_MIN_COLS_LOG_31;
+  static constexpr bool PASS1_FULL_TABLE = NTT_31_PASS1_TABLE;
+  static constexpr bool NARROW_FIRST = true;
+  static constexpr bool SHOUP_OUTER = false;
+  static constexpr bool LDS_TW = true;
+  static constexpr int WAVES_PER_EU = 4;
+  static constexpr bool LDS_SPLIT = false;
+  static constexpr bool FASTRED = false;
+  struct Tw {
+    uint32_t w[1];  // canonical w
+    uint32_t ws;    // floor(w 2^32 / p)
+  };
+  struct Args {
+    uint32_t p;
+    uint32_t pinv;  // p^-1 mod 2^32 (Montgomery products)
+    Tw w8[3];       // w_8^1, w_8^2, w_8^3
+    Tw ninv;        // n^-1
+    uint32_t* dbg;  // debug builds: the plan's status word (NTT_DBG_*); null otherwise
+  };
+  __device__ static bool dbg_canonical(const uint32_t (&x)[W], const Args& A) { return f31::is_canonical(x[0], A.p); }
+  template <int MW = MEMW>
+  __device__ static __forceinline__ void load(uint32_t (&x)[W], const uint32_t* __restrict__ base, size_t idx) {
+    static_assert(MW == 1, "HBM width");
+    x[0] = base[idx];
+  }
+  template <int FROM, int TO, bool FAST = false, bool R32 = true>
+  __device__ static __forceinline__ void reduce(uint32_t (&)[W], const Args&) {}  // always canonical
+  // scratch between passes: canonical like everything else (the "lazy" check of the debug build
+  // degenerates to the canonical one)
+  template <int BOUND, bool FAST = false, int MW = MEMW, bool WT = false>
+  __device__ static __forceinline__ void store_lazy(uint32_t* __restrict__ base, size_t idx, uint32_t (&x)[W],
+                                                    [[maybe_unused]] const Args& A) {
+    static_assert(MW == 1 && !WT, "HBM width; write-through stores: Eng29 engines only");
+#if NTT_DEBUG_CHECKS
+    if (!f31::is_canonical(x[0], A.p)) ntt_dbg_flag(A.dbg, NTT_DBG_LAZY);
+#endif
+    base[idx] = x[0];
+  }
+  template <int BOUND, bool FAST = false, int MW = MEMW>
+  __device__ static __forceinline__ void store(uint32_t* __restrict__ base, size_t idx, uint32_t (&x)[W],
+                                               [[maybe_unused]] const Args& A) {
+    static_assert(MW == 1, "HBM width");
+#if NTT_DEBUG_CHECKS
+    if (!f31::is_canonical(x[0], A.p)) ntt_dbg_flag(A.dbg, NTT_DBG_OUTPUT);
+#endif
+    base[idx] = x[0];
+  }
+  __device__ static __forceinline__ void tload(Tw& t, const uint32_t* __restrict__ tab, size_t idx) {
+    const uint2 v = reinterpret_cast<const uint2*>(tab)[idx];
+    t.w[0] = v.x;
+    t.ws = v.y;
+  }
+  __device__ static __forceinline__ void tload_lds(Tw& t, const uint32_t* lds_tw, uint32_t idx) {
+    const uint2 v = reinterpret_cast<const uint2*>(lds_tw)[idx];
+    t.w[0] = v.x;
+    t.ws = v.y;
+  }
+  // any 32-bit x (a caller's non-canonical word included): x w mod p
+  __device__ static __forceinline__ void mul(uint32_t (&x)[W], const Tw& t, const Args& A) {
+    x[0] = f31::mulc(x[0], t.w[0], t.ws, A.p);
+  }
+  __device__ static __forceinline__ void mul_u(uint32_t (&x)[W], const Tw& t, const Args& A) { mul(x, t, A); }
+  // x y 2^-32 mod p for x y < 2^32 p
+  __device__ static __forceinline__ void mulv(uint32_t (&x)[W], const uint32_t (&y)[W], const Args& A) {
+    x[0] = f31::mulv(x[0], y[0], A.p, A.pinv);
+  }
+  // DIF butterfly on canonical values: (a + b, a - b)
+  template <int K>
+  __device__ static __forceinline__ void bfly_l(uint32_t (&a)[W], uint32_t (&b)[W], const Args& A) {
+    const uint32_t x = a[0], y = b[0];
+    a[0] = f31::add(x, y, A.p);
+    b[0] = f31::sub(x, y, A.p);
+  }
+  template <int K>
+  __device__ static __forceinline__ void bfly_w_l(uint32_t (&a)[W], uint32_t (&b)[W], const Tw& t, const Args& A) {
+    const uint32_t x = a[0], y = b[0];
+    a[0] = f31::add(x, y, A.p);
+    b[0] = f31::mulc(f31::sub_lazy(x, y, A.p), t.w[0], t.ws, A.p);
   }
 };
 

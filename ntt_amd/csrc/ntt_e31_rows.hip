@@ -1,0 +1,5 @@
+// Eng31 (primes below 2^31, 4-B elements): k_pass instantiations for KIND_ROWS (several single-tile transforms per workgroup).
+#include "ntt_kernels_impl.hpp"
+namespace ntt {
+NTT_INSTANTIATE_KIND(Eng31, KIND_ROWS)
+}  // namespace ntt

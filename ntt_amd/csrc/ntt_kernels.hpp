@@ -33,7 +33,7 @@ constexpr int kRowsMinLog = 3;
 // 256-bit engines (1024-element tiles, 256-thread workgroups); 2^6 on P, whose 8192-element tiles
 // make 1024-thread workgroups that lose to one transform per workgroup from 2^7 up (+20 %, 2^8 +180 %)
 // (Goldilocks, W = 2: 4096-element tiles and 512-thread workgroups, the P path's shape; its limit is
-// taken from P, not measured)
+// taken from P, not measured; Eng31, W = 1: P's own shape, its limit taken from P as well)
 template <class E>
 constexpr int rows_max_log() {
   return E::W <= 2 ? 6 : 7;
@@ -76,6 +76,10 @@ struct HasRows<EngP> {  // P469762049 (the reference's own field), ntt_ep_rows.h
 };
 template <>
 struct HasRows<Eng64G> {  // Goldilocks, ntt_eg_rows.hip
+  static constexpr bool value = true;
+};
+template <>
+struct HasRows<Eng31> {  // primes below 2^31 on 4-B elements, ntt_e31_rows.hip
   static constexpr bool value = true;
 };
 

@@ -2033,7 +2033,9 @@ __global__ void k_fill_random(uint32_t* __restrict__ dst, size_t n, uint64_t see
                               FillMap fm) {
   NTT_GRID_STRIDE(i, n) {
     const uint64_t j = fill_index(i, fm);
-    if constexpr (MEMW == 2) {
+    if constexpr (MEMW == 1) {  // 4-B elements: the low limb's draw masked below 2^31 (top_bits <= 30)
+      dst[i] = (uint32_t)(splitmix64((seed << 32) + 4 * j) & ((1ull << top_bits) - 1));
+    } else if constexpr (MEMW == 2) {
       const uint64_t v = splitmix64((seed << 32) + 4 * j) & ((1ull << top_bits) - 1);
       reinterpret_cast<uint2*>(dst)[i] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));  // P: top_bits < 32
     } else {
@@ -2059,7 +2061,9 @@ template <int MEMW>
 __global__ void k_fill_iota(uint32_t* __restrict__ dst, size_t n, FillMap fm) {
   NTT_GRID_STRIDE(i, n) {
     const uint64_t j = fill_index(i, fm);
-    if constexpr (MEMW == 2) {
+    if constexpr (MEMW == 1) {  // 4-B elements: the index's low word (plans of at most 2^27 points)
+      dst[i] = (uint32_t)j;
+    } else if constexpr (MEMW == 2) {
       reinterpret_cast<uint2*>(dst)[i] = make_uint2((uint32_t)j, (uint32_t)((uint64_t)j >> 32));
     } else {
       uint4* p = reinterpret_cast<uint4*>(dst + i * MEMW);

@@ -381,6 +381,8 @@ extern "C" {
 int ntt_mplan_create(ntt_mplan** out, int field_id, unsigned log_n, unsigned limbs64, int ngpus, const int* devices) {
   if (!out || ngpus < 1 || (ngpus & (ngpus - 1)) || !devices) return NTT_ERR_ARG;
   *out = nullptr;
+  // the exchange sizes count 8-byte words (chunk_words, exchange pieces): no 4-byte elements
+  if (field_id == NTT_FIELD_BABYBEAR || field_id == NTT_FIELD_KOALABEAR) return NTT_ERR_ARG;
   DeviceGuard guard;
   auto m = new ntt_mplan();
   m->ngpus = ngpus;

@@ -365,6 +365,30 @@ static bool schedule(unsigned log_n, unsigned tile_log, unsigned min_cols_log, b
   return true;
 }
 
+// The schedule of an engine: schedule() at the engine's MIN_COLS_LOG (the narrowest column group its
+// kernels are instantiated for).  An engine may name a wider group it prefers (PrefColsLog): that
+// schedule is taken instead wherever it exists with the same number of passes.
+template <class E>
+struct PrefColsLog {
+  static constexpr unsigned value = E::MIN_COLS_LOG;
+};
+template <>
+struct PrefColsLog<Eng31> {
+  static constexpr unsigned value = Eng31::PREF_COLS_LOG;
+};
+template <class E>
+static bool schedule_for(unsigned log_n, unsigned* r, unsigned& p) {
+  if (!schedule(log_n, E::TILE_LOG, E::MIN_COLS_LOG, E::NARROW_FIRST, r, p)) return false;
+  if constexpr (PrefColsLog<E>::value > (unsigned)E::MIN_COLS_LOG) {
+    const char* forced = getenv("NTT_SCHEDULE");
+    unsigned r2[8] = {0}, p2 = 0;
+    if (p >= 2 && !(forced && *forced) &&
+        schedule(log_n, E::TILE_LOG, PrefColsLog<E>::value, E::NARROW_FIRST, r2, p2) && p2 == p)
+      for (unsigned i = 0; i < p; ++i) r[i] = r2[i];
+  }
+  return true;
+}
+
 // NTT_PLAN_IN_PLACE: a palindromic sequence (r_i = r_{p-1-i}, 3 <= r_i <= rmax, schedule_ok) with the
 // fewest passes (>= p0), then the smallest largest radix, then the largest smallest one.  The digit
 // reversal of a palindromic sequence is an involution (k_digitrev_swap).
@@ -561,6 +585,35 @@ struct EngHost<Eng64G> {
   }
 };
 
+// Eng31: one 32-bit host word; twiddle entries are Shoup pairs, element-format entries w 2^32 mod p (the
+// Montgomery radix of Eng31::mulv), like the P path's, on any odd modulus below 2^31.
+template <>
+struct EngHost<Eng31> {
+  static constexpr int NH = 1;
+  using EA = Eng31::Args;
+  using ET = Eng31::Tw;
+  HostField<NH> const* H = nullptr;
+  void init(const HostField<NH>& h) { H = &h; }
+  void encode(const Vec<NH>& c, uint32_t* out) const {
+    out[0] = c[0];
+    out[1] = f31::shoup_companion(c[0], H->M.p[0]);
+  }
+  void encode_scaled(const Vec<NH>& c, uint32_t* out) const { encode(H->to_mont(c), out); }
+  bool check_modulus(const uint32_t* p) const { return f31::modulus_ok(p[0]); }
+  void fill_args(EA& A, const uint32_t* p, const Vec<NH>* w8, const Vec<NH>& ninv) const {
+    A.p = p[0];
+    A.pinv = f31::pinv32(p[0]);
+    uint32_t t[2];
+    auto tw = [&](const Vec<NH>& c, ET& e) {
+      encode(c, t);
+      e.w[0] = t[0];
+      e.ws = t[1];
+    };
+    for (int k = 0; k < 3; ++k) tw(w8[k], A.w8[k]);
+    tw(ninv, A.ninv);
+  }
+};
+
 template <class E>
 struct PlanImpl final : PlanBase {
   static constexpr int NH = EngHost<E>::NH;
@@ -729,8 +782,7 @@ struct PlanImpl final : PlanBase {
     }
 
     // ---- schedule + tables (engine-encoded)
-    if (!schedule(log_n, tile_log_of<E>(), E::MIN_COLS_LOG, E::NARROW_FIRST, r, npass))
-      return NTT_ERR_ARG;
+    if (!schedule_for<E>(log_n, r, npass)) return NTT_ERR_ARG;
     if (flags & NTT_PLAN_IN_PLACE) {
       // passes store their lazily reduced values where they read them: the scratch element must be
       // the caller's element
@@ -786,7 +838,8 @@ struct PlanImpl final : PlanBase {
       off_bealto_pq = push_powers(H.pow_u64(w, n >> bealto_max_deg), 1ull << (bealto_max_deg - 1), nullptr);
     }
     {  // pointwise product constants: mulv leaves a b / R_e (R_e the engine's Montgomery radix);
-       // multiplying by R_e gives a b, by R_e R^-1 the Montgomery product a b R^-1 (R = 2^(64 limbs64))
+       // multiplying by R_e gives a b, by R_e R^-1 the Montgomery product a b R^-1 (R = 2^(64 limbs64);
+       // 2^32 on the 4-byte elements of Eng31)
       off_r2 = host.size();
       uint32_t enc[TW];
       EH.encode(engine_radix_mod_p(), enc);
@@ -794,7 +847,8 @@ struct PlanImpl final : PlanBase {
       while (host.size() % 4) host.push_back(0);
       Vec<NH> rio{};  // R = 2^(64 limbs64) mod p by doubling
       rio[0] = 1;
-      for (int k = 0; k < 64 * ((NH + 1) / 2); ++k) rio = H.add(rio, rio);
+      constexpr int kIoBits = std::is_same_v<E, Eng31> ? 32 : 64 * ((NH + 1) / 2);
+      for (int k = 0; k < kIoBits; ++k) rio = H.add(rio, rio);
       const Vec<NH> rio_inv = H.from_mont(H.pow(H.to_mont(rio), pm2));
       off_rm = host.size();
       EH.encode(H.from_mont(H.mul(H.to_mont(engine_radix_mod_p()), H.to_mont(rio_inv))), enc);
@@ -1287,7 +1341,7 @@ struct PlanImpl final : PlanBase {
 
   // canonical value of the engine's Montgomery radix R_e mod p
   Vec<NH> engine_radix_mod_p() const {
-    if constexpr (IsEng32<E>::value) {
+    if constexpr (IsEng32<E>::value || std::is_same_v<E, Eng31>) {
       return H.r1;  // 2^(32N) mod p
     } else if constexpr (std::is_same_v<E, Eng64G>) {
       Vec<NH> one{};  // plain canonical values: no radix
@@ -1329,13 +1383,12 @@ struct PlanImpl final : PlanBase {
 
   unsigned passes_for(unsigned log_x) const override {
     unsigned rr[8] = {0}, p = 0;
-    if (!schedule(log_x, tile_log_of<E>(), E::MIN_COLS_LOG, E::NARROW_FIRST, rr, p))
-      return 99;
+    if (!schedule_for<E>(log_x, rr, p)) return 99;
     return p == 0 ? 1 : p;
   }
   unsigned max_radix_for(unsigned log_x) const override {
     unsigned rr[8] = {0}, p = 0;
-    if (!schedule(log_x, tile_log_of<E>(), E::MIN_COLS_LOG, E::NARROW_FIRST, rr, p)) return 99;
+    if (!schedule_for<E>(log_x, rr, p)) return 99;
     unsigned m = p == 0 ? log_x : 0;
     for (unsigned i = 0; i < p; ++i) m = rr[i] > m ? rr[i] : m;
     return m;
@@ -2029,11 +2082,13 @@ struct FieldDef {
   uint64_t p[4];
   uint64_t g;
 };
-static const FieldDef kFields[4] = {
+static const FieldDef kFields[6] = {
     {{469762049ull, 0, 0, 0}, 3},
     {{0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}, 5},
     {{0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull}, 7},
     {{kGoldilocksP, 0, 0, 0}, 7},
+    {{0x78000001ull, 0, 0, 0}, 31},  // BabyBear, 2^31 - 2^27 + 1
+    {{0x7f000001ull, 0, 0, 0}, 3},   // KoalaBear, 2^31 - 2^24 + 1
 };
 
 static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const uint64_t* g64, unsigned limbs64,
@@ -2044,6 +2099,12 @@ static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const 
   if (rivals & (rivals - 1)) return NTT_ERR_ARG;  // one rival schedule per plan
   if ((flags & NTT_PLAN_IN_PLACE) && (rivals || (flags & NTT_PLAN_TWIDDLE_ONLY)))
     return NTT_ERR_ARG;
+  // NTT_PLAN_ELEM32 (4-B elements, Eng31): one limb, a modulus below 2^31, the default schedule only
+  const bool elem32 = (flags & NTT_PLAN_ELEM32) != 0;
+  if (elem32) {
+    if (limbs64 != 1 || rivals || (flags & NTT_PLAN_IN_PLACE)) return NTT_ERR_ARG;
+    if (!f31::modulus_ok(p64[0])) return NTT_ERR_FIELD;
+  }
   // Goldilocks (8-B elements, Eng64G): the default schedule only
   const bool goldilocks = limbs64 == 1 && p64[0] == kGoldilocksP;
   if (goldilocks && (rivals || (flags & (NTT_PLAN_IN_PLACE | NTT_PLAN_MONTGOMERY_IO)))) return NTT_ERR_ARG;
@@ -2058,7 +2119,11 @@ static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const 
     g32[2 * i + 1] = (uint32_t)(g64[i] >> 32);
   }
   int rc;
-  if (goldilocks) {
+  if (elem32) {
+    auto impl = std::make_unique<PlanImpl<Eng31>>();
+    rc = impl->init(p32, g32, log_n, device, flags);
+    out = std::move(impl);
+  } else if (goldilocks) {
     auto impl = std::make_unique<PlanImpl<Eng64G>>();
     rc = impl->init(p32, g32, log_n, device, flags);
     out = std::move(impl);
@@ -2238,10 +2303,15 @@ int ntt_plan_create(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs
 
 static int create_field_plan(ntt_plan** out, int field_id, unsigned log_n, unsigned limbs64, int device,
                              unsigned flags, bool allow_wide) {
-  if (field_id < 0 || field_id > 3) return set_err(NTT_ERR_ARG);
+  if (field_id < 0 || field_id > 5) return set_err(NTT_ERR_ARG);
   if (limbs64 != 1 && limbs64 != 4 && limbs64 != 6) return set_err(NTT_ERR_ARG);
-  if (limbs64 == 1 && field_id != NTT_FIELD_P469762049 && field_id != NTT_FIELD_GOLDILOCKS) return set_err(NTT_ERR_ARG);
+  const bool field31 = field_id == NTT_FIELD_BABYBEAR || field_id == NTT_FIELD_KOALABEAR;
+  if (limbs64 == 1 && field_id != NTT_FIELD_P469762049 && field_id != NTT_FIELD_GOLDILOCKS && !field31)
+    return set_err(NTT_ERR_ARG);
   if (field_id == NTT_FIELD_GOLDILOCKS && limbs64 != 1) return set_err(NTT_ERR_ARG);  // 8-byte elements only
+  if (field31 && limbs64 != 1) return set_err(NTT_ERR_ARG);                            // 4-byte elements only
+  if (field31) flags |= NTT_PLAN_ELEM32;  // implied
+  else if (flags & NTT_PLAN_ELEM32) return set_err(NTT_ERR_ARG);  // fields 0-3 keep their element layouts
   const FieldDef& F = kFields[field_id];
   uint64_t p[6] = {0}, g[6] = {0};
   for (unsigned i = 0; i < limbs64 && i < 4; ++i) p[i] = F.p[i];

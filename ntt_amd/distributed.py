@@ -268,9 +268,10 @@ class RankPlan:
         _L.check(self.lib.ntt_rplan_create(C.byref(h), field_id, log_n, limbs64, world, rank, device),
                  "ntt_rplan_create")
         self.handle = h
-        n1, n2 = C.c_uint(), C.c_uint()
-        _L.check(self.lib.ntt_rplan_info(h, None, None, C.byref(n1), C.byref(n2), None), "ntt_rplan_info")
+        n1, n2, eb = C.c_uint(), C.c_uint(), C.c_uint()
+        _L.check(self.lib.ntt_rplan_info(h, None, None, C.byref(n1), C.byref(n2), C.byref(eb)), "ntt_rplan_info")
         self.layout = Layout(log_n, world, rank, n2.value)
+        self.elem_bytes = eb.value  # 4: the int32 tensors of the BabyBear / KoalaBear plans
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -280,7 +281,8 @@ class RankPlan:
 
     def empty(self, count: int) -> torch.Tensor:
         shape = (count,) if self.limbs64 == 1 else (count, self.limbs64)
-        return torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+        dtype = torch.int32 if self.elem_bytes == 4 else torch.int64
+        return torch.empty(shape, dtype=dtype, device=f"cuda:{self.device}")
 
     @staticmethod
     def _p(t):

@@ -5,12 +5,16 @@ P469762049 = 469762049  # 7 * 2^26 + 1, generator 3 (reference GZKP-NTT.cu:7-8)
 BN254_FR = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 BLS12_381_FR = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 GOLDILOCKS = 0xFFFFFFFF00000001  # 2^64 - 2^32 + 1, generator 7, two-adicity 32 (8-byte elements, 1 limb)
+BABYBEAR = 0x78000001  # 2^31 - 2^27 + 1, generator 31, two-adicity 27 (4-byte elements, 1 limb)
+KOALABEAR = 0x7F000001  # 2^31 - 2^24 + 1, generator 3, two-adicity 24 (4-byte elements, 1 limb)
 
 FIELDS = {
     0: ("P469762049", P469762049, 3),
     1: ("BN254_FR", BN254_FR, 5),
     2: ("BLS12_381_FR", BLS12_381_FR, 7),
     3: ("GOLDILOCKS", GOLDILOCKS, 7),
+    4: ("BABYBEAR", BABYBEAR, 31),
+    5: ("KOALABEAR", KOALABEAR, 3),
 }
 
 

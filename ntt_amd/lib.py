@@ -19,6 +19,8 @@ NTT_FIELD_P469762049 = 0
 NTT_FIELD_BN254_FR = 1
 NTT_FIELD_BLS12_381_FR = 2
 NTT_FIELD_GOLDILOCKS = 3
+NTT_FIELD_BABYBEAR = 4
+NTT_FIELD_KOALABEAR = 5
 NTT_PLAN_TWIDDLE_ONLY = 1
 NTT_PLAN_MONTGOMERY_IO = 2
 NTT_PLAN_STOCKHAM = 4
@@ -32,6 +34,7 @@ NTT_PLAN_IMPROVED_V1 = 512
 NTT_PLAN_IMPROVED_V2 = 1024
 NTT_PLAN_IMPROVED_V3 = 2048
 NTT_PLAN_IMPROVED_V4 = 4096
+NTT_PLAN_ELEM32 = 8192
 
 # Every symbol declared in include/ntt.h with its ctypes prototype: (restype, argtypes).
 _vp = C.c_void_p

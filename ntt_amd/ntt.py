@@ -41,10 +41,16 @@ def int_to_limbs(v: int, limbs64: int) -> List[int]:
     return [(v >> (64 * i)) & ((1 << 64) - 1) for i in range(limbs64)]
 
 
-def host_array(values: Iterable[int], limbs64: int) -> np.ndarray:
+def host_array(values: Iterable[int], limbs64: int, elem32: bool = False) -> np.ndarray:
     """Python ints -> host array in the cgbn_mem_t layout: int64 bit patterns, [n, limbs64] ([n] for
-    1 limb).  One-limb values go through uint64, so elements >= 2^63 (Goldilocks) keep their bits."""
+    1 limb).  One-limb values go through uint64, so elements >= 2^63 (Goldilocks) keep their bits.
+    ``elem32`` (one limb only): the 4-byte layout of NTT_PLAN_ELEM32 plans, int32 bit patterns of
+    uint32 elements, [n]."""
     vals = list(values)
+    if elem32:
+        if limbs64 != 1:
+            raise ValueError("4-byte elements are one limb")
+        return np.array([int(v) & 0xFFFFFFFF for v in vals], dtype=np.uint32).view(np.int32)
     if limbs64 == 1:
         return np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in vals], dtype=np.uint64).view(np.int64)
     host = np.zeros((len(vals), limbs64), dtype=np.uint64)
@@ -55,7 +61,10 @@ def host_array(values: Iterable[int], limbs64: int) -> np.ndarray:
 
 
 def host_ints(host: np.ndarray) -> List[int]:
-    """Host array in the cgbn_mem_t layout (host_array) -> Python ints (unsigned)."""
+    """Host array in the cgbn_mem_t layout (host_array) -> Python ints (unsigned).  An int32 / uint32
+    array is the 4-byte layout (``host_array(..., elem32=True)``)."""
+    if host.dtype.itemsize == 4:
+        return [int(v) for v in host.view(np.uint32)]
     if host.ndim == 1:
         return [int(v) for v in host.view(np.uint64)]
     u = host.view(np.uint64)
@@ -68,13 +77,14 @@ def host_ints(host: np.ndarray) -> List[int]:
     return out
 
 
-def to_device(values: Iterable[int], limbs64: int, device="cuda") -> torch.Tensor:
-    """Python ints -> device tensor in the cgbn_mem_t layout (int64 [n, limbs64]; [n] for 1 limb)."""
-    return torch.from_numpy(host_array(values, limbs64)).to(device)
+def to_device(values: Iterable[int], limbs64: int, device="cuda", elem32: bool = False) -> torch.Tensor:
+    """Python ints -> device tensor in the cgbn_mem_t layout (int64 [n, limbs64]; [n] for 1 limb;
+    ``elem32``: int32 [n], the 4-byte layout of NTT_PLAN_ELEM32 plans)."""
+    return torch.from_numpy(host_array(values, limbs64, elem32)).to(device)
 
 
 def from_device(t: torch.Tensor) -> List[int]:
-    """Device tensor (cgbn_mem_t layout) -> Python ints."""
+    """Device tensor (cgbn_mem_t layout, or int32: the 4-byte layout) -> Python ints."""
     return host_ints(t.detach().cpu().numpy())
 
 
@@ -88,14 +98,16 @@ class NTTPlan:
     ``field_id`` selects a built-in field (0 P469762049, 1 BN254 Fr, 2 BLS12-381 Fr, 3 Goldilocks
     with ``limbs64=1``: int64 bit patterns of uint64 elements); or pass
     ``modulus``/``generator`` ints for any odd prime below 2^(64*limbs64 - 1) with 2^log_n | p - 1
-    (big-num.cu's modulus-generic path).
+    (big-num.cu's modulus-generic path).  Fields 4 (BabyBear) and 5 (KoalaBear) with ``limbs64=1``,
+    and custom one-limb plans with ``elem32=True`` (any odd prime below 2^31), work on 4-byte
+    elements: contiguous ``torch.int32`` tensors of shape ``[batch * n]`` (uint32 bit patterns).
     """
 
     def __init__(self, field_id: int = 1, log_n: int = 10, limbs64: int = 4, device: int = 0,
                  modulus: Optional[int] = None, generator: Optional[int] = None, twiddle_only: bool = False,
                  montgomery_io: bool = False, stockham: bool = False, gzkp: bool = False,
                  in_place: bool = False, single_launch: bool = False, naive: bool = False,
-                 no_swap: bool = False, bealto: str = ""):
+                 no_swap: bool = False, bealto: str = "", elem32: bool = False):
         if bealto and bealto not in BEALTO_FLAGS:
             raise ValueError(f"bealto must be one of {sorted(BEALTO_FLAGS)}, not {bealto!r}")
         self._lib = _L.load()
@@ -126,6 +138,8 @@ class NTTPlan:
         flags |= _L.NTT_PLAN_IN_PLACE if in_place else 0
         # single_launch: 3-pass transforms as one persistent launch (BASELINE config 2's single kernel)
         flags |= _L.NTT_PLAN_SINGLE_LAUNCH if single_launch else 0
+        # elem32: 4-byte elements (ntt.h NTT_PLAN_ELEM32; implied by the BabyBear / KoalaBear fields)
+        flags |= _L.NTT_PLAN_ELEM32 if elem32 else 0
         self.montgomery_io = bool(montgomery_io)
         if modulus is None:
             st = self._lib.ntt_plan_create_ex(C.byref(h), int(field_id), self.log_n, self.limbs64, self.device, flags)
@@ -141,19 +155,22 @@ class NTTPlan:
         radix = (C.c_uint * 8)()
         _L.check(self._lib.ntt_plan_info(h, C.byref(n), C.byref(eb), C.byref(npass), radix), "ntt_plan_info")
         self.elem_bytes = eb.value
+        self.elem32 = self.elem_bytes == 4
+        self.dtype = torch.int32 if self.elem32 else torch.int64  # the tensors the plan takes
         self.passes = [radix[i] for i in range(npass.value)]
 
     # -------------------------------------------------------------------------------- memory
     def empty(self, batch: int = 1) -> torch.Tensor:
         shape = (batch * self.n,) if self.limbs64 == 1 else (batch * self.n, self.limbs64)
-        return torch.empty(shape, dtype=torch.int64, device=f"cuda:{self.device}")
+        return torch.empty(shape, dtype=self.dtype, device=f"cuda:{self.device}")
 
     def _check_tensor(self, t: torch.Tensor, batch: int = 1) -> None:
         if not t.is_cuda:
             raise ValueError("NTT data must be a device (HIP) tensor")
-        if not t.is_contiguous() or t.dtype != torch.int64:
-            raise ValueError("NTT data must be a contiguous int64 tensor in the cgbn_mem_t layout")
-        if t.numel() * 8 != batch * self.n * self.elem_bytes:
+        if not t.is_contiguous() or t.dtype != self.dtype:
+            raise ValueError("NTT data must be a contiguous int64 tensor in the cgbn_mem_t layout"
+                             if not self.elem32 else "NTT data must be a contiguous int32 tensor (4-byte elements)")
+        if t.numel() * t.element_size() != batch * self.n * self.elem_bytes:
             raise ValueError(f"expected {batch * self.n} elements of {self.elem_bytes} bytes")
         if t.device.index != self.device:
             raise ValueError(f"tensor on {t.device}, plan on cuda:{self.device}")
@@ -187,8 +204,8 @@ class NTTPlan:
 
     def count_noncanonical(self, t: torch.Tensor, stream=None) -> int:
         """Number of elements of t that are not < p (the transforms' input contract); blocking."""
-        if t.device.type != "cuda" or not t.is_contiguous() or t.dtype != torch.int64:
-            raise ValueError("expected a contiguous int64 device tensor in the element layout")
+        if t.device.type != "cuda" or not t.is_contiguous() or t.dtype != self.dtype:
+            raise ValueError("expected a contiguous device tensor in the plan's element layout")
         count = t.numel() if self.limbs64 == 1 else t.numel() // self.limbs64
         bad = C.c_uint64()
         _L.check(self._lib.ntt_count_noncanonical(self._h, C.c_void_p(t.data_ptr()), count, C.byref(bad),
@@ -259,7 +276,7 @@ class NTTPlan:
     def fill_map(self, t: torch.Tensor, kind: str, seed: int, row0: int, log_inner: int, log_stride: int,
                  stream=None) -> torch.Tensor:
         """Local element i <- synthetic value of global j = row0 + (i >> log_inner) + ((i & m) << log_stride)."""
-        count = t.numel() * 8 // self.elem_bytes
+        count = t.numel() * t.element_size() // self.elem_bytes
         k = {"iota": 0, "random": 1}[kind]
         _L.check(self._lib.ntt_fill_map(self._h, C.c_void_p(t.data_ptr()), count, k, int(seed), int(row0),
                                         int(log_inner), int(log_stride), _stream_ptr(stream, t.device)),
