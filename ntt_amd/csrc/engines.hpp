@@ -181,8 +181,10 @@ struct Eng29 {
   }
   __device__ static bool dbg_canonical(const uint32_t (&x)[W], const Args& A) { return dbg_below(x, A.kp[0]); }
   // Padded offsets: value K p, limbs c_0 = kp_0 + P, c_i = kp_i + P - P/2^29 (0 < i < 8),
-  // c_8 = kp_8 - P/2^29, so that c_i >= P > b_i for limb bound P and a - b + C never goes negative
-  // limb-wise; K = (value bound of b) + 1 keeps the top limb non-negative when p_top >= 3.
+  // c_8 = kp_8 - P/2^29, so that c_0 >= P and c_i >= P - P/2^29 (with equality where a limb of K p is
+  // zero, e.g. p = 2^250 + small) and a - b + C never goes negative limb-wise for b_i <= P - P/2^29:
+  // normalised limbs (<= 2^29 - 1) under P = 2^29, sums of two of them (<= 2^30 - 2) under P = 2^30.
+  // K = (value bound of b) + 1 keeps the top limb non-negative when p_top >= 3.
   enum : int { PC_5_29 = 0, PC_9_30 = 1, PC_4_29 = 2, PC_17_29 = 3, PC_7_30 = 4 };
 
   // The 256-bit class in the 48-B layout (W32 = 12) reads only the first 32 B of an element: its

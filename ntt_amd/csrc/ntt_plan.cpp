@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/ntt.h"
+#include "eng29_args.hpp"
 #include "ntt_internal.hpp"
 #include "ntt_kernels.hpp"
 
@@ -479,19 +480,7 @@ struct EngHost<Eng29<L, W32, S, T>> {
     return bits <= 32 * NH - 1 && bits <= 29 * L - 6;
   }
   void fill_args(EA& A, const uint32_t* p, const Vec<NH>* w8, const Vec<NH>& ninv) const {
-    uint32_t pw[NH];
-    for (int i = 0; i < NH; ++i) pw[i] = p[i];
-    pack29<L, NH>(A.M.p, pw);
-    for (int i = 0; i < L; ++i) A.kp[0][i] = A.M.p[i];
-    for (int j = 1; j < 5; ++j) {  // 2^j p: double the normalised limbs and renormalise
-      for (int i = 0; i < L; ++i) A.kp[j][i] = A.kp[j - 1][i] << 1;
-      norm_u<L>(A.kp[j]);
-    }
-    for (int i = 0; i < L; ++i) A.M.p2[i] = A.kp[1][i];
-    neg29<L>(A.pbar, A.M.p);
-    uint32_t inv = 1;
-    for (int i = 0; i < 5; ++i) inv *= 2 - p[0] * inv;
-    A.M.pinv = (0u - inv) & kMask29;
+    eng29_fill_consts<E29, L, NH>(A, p);  // eng29_args.hpp: everything but the twiddles
     uint32_t tmp[TW];
     auto to_tw = [&](const Vec<NH>& c, typename E29::Tw& t) {
       encode(c, tmp);
@@ -502,29 +491,6 @@ struct EngHost<Eng29<L, W32, S, T>> {
     };
     for (int k = 0; k < 3; ++k) to_tw(w8[k], A.w8[k]);
     to_tw(ninv, A.ninv);
-    const uint32_t ptop = A.M.p[L - 1];
-    A.red_ok = ptop >= (1u << 18) ? 1u : 0u;
-    A.red_inv = std::nextafter(1.0f / (float)(ptop + 1u), 0.0f);
-    // padded offsets for the unnormalised butterflies (used only when red_ok: p_top >= 3)
-    auto padded = [&](uint32_t K, uint32_t pad, uint32_t* c) {
-      uint32_t kp[L];
-      uint64_t carry = 0;
-      for (int i = 0; i < L; ++i) {
-        const uint64_t v = (uint64_t)A.M.p[i] * K + carry;
-        kp[i] = (uint32_t)v & kMask29;
-        carry = v >> 29;
-      }
-      kp[L - 1] += (uint32_t)(carry << 29);  // K p < 2^(29L): carry is 0 for the supported fields
-      const uint32_t b = pad >> 29;
-      c[0] = kp[0] + pad;
-      for (int i = 1; i + 1 < L; ++i) c[i] = kp[i] + pad - b;
-      c[L - 1] = kp[L - 1] - b;
-    };
-    padded(5, 1u << 29, A.pc[E29::PC_5_29]);
-    padded(9, 1u << 30, A.pc[E29::PC_9_30]);
-    padded(4, 1u << 29, A.pc[E29::PC_4_29]);
-    padded(17, 1u << 29, A.pc[E29::PC_17_29]);
-    padded(7, 1u << 30, A.pc[E29::PC_7_30]);
   }
 };
 
