@@ -229,13 +229,36 @@ int ntt_inverse(ntt_plan* plan, void* d_data, void* hip_stream);
 int ntt_forward_batch(ntt_plan* plan, void* d_data, unsigned batch, void* hip_stream);
 int ntt_inverse_batch(ntt_plan* plan, void* d_data, unsigned batch, void* hip_stream);
 
-/* Coset NTT, the low-degree-extension step of the GZKP provers the reference targets:
+/* Coset NTT of one vector of the plan's own size, in place:
  *   forward:  X_k = sum_j x_j (c w^k)^j = NTT(x_j c^j)          (evaluations on the coset c<w>)
  *   inverse:  x_j = c^-j INTT(X)_j                               (interpolation from the coset)
  * `shift` = c as limbs64 little-endian 64-bit limbs, canonical and nonzero (e.g. the field's
- * multiplicative generator).  The plan caches the c^j tables of the last shift. */
+ * multiplicative generator).  The plan caches the c^j tables of the last shift.  This is not a
+ * low-degree extension: it neither pads nor batches (ntt_lde_batch below does). */
 int ntt_forward_coset(ntt_plan* plan, void* d_data, const uint64_t* shift, void* hip_stream);
 int ntt_inverse_coset(ntt_plan* plan, void* d_data, const uint64_t* shift, void* hip_stream);
+
+/* Low-degree extension.  `plan` is a plan of the LARGE size N = 2^log_n.  d_in holds `batch`
+ * polynomials back to back, n = 2^(log_n - log_blowup) coefficients each (stride n elements);
+ * d_out receives `batch` vectors of N evaluations each (stride N elements), natural order:
+ *     out[v][k] = sum_{j < n} in[v][j] (c w_N^k)^j ,   c = *shift, or 1 when shift == NULL.
+ * d_in is not modified.  Asynchronous on hip_stream.
+ * 0 <= log_blowup <= log_n: 0 is an out-of-place batched coset forward, log_n extends constants.
+ * `shift` follows ntt_forward_coset (canonical, nonzero, limbs64 words; canonical also on
+ * NTT_PLAN_MONTGOMERY_IO plans, whose data stay in Montgomery form) and shares its cached tables
+ * (except on 4-limb plans of 2^20, where ntt_forward_coset runs on the plan's 4096-element tiles
+ * with a cache of its own); a call with shift == NULL leaves the cached shift as it is.
+ * The zero padding is never written or read: the first pass loads the n coefficients of each
+ * polynomial, multiplied by c^j at that load (6-limb moduli above 2^255 and plans without the fast
+ * reductions: by one launch over the batch n inputs before it), and takes every other input from
+ * registers.  Sizes up to 4 points, and a few custom-modulus plans whose first pass has no such form
+ * (DESIGN.md section 4), stage the zero-padded vectors in d_out instead.
+ * NTT_ERR_ARG before any launch: a null plan or pointer, batch == 0, log_blowup > log_n, a bad
+ * shift, overlapping byte ranges of d_in (batch n elements) and d_out (batch N elements),
+ * NTT_PLAN_TWIDDLE_ONLY and NTT_PLAN_IN_PLACE plans.  Rival-schedule and NTT_PLAN_SINGLE_LAUNCH
+ * plans run it on the default schedule; 4-limb plans of 2^20 on their 1024-element tiles. */
+int ntt_lde_batch(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
+                  unsigned batch, void* hip_stream);
 
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */

@@ -34,6 +34,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 SOURCES = ["ntt_e256_fused.hip"]  # the fused single-launch 3-pass schedule (NTT_PLAN_SINGLE_LAUNCH)
 SOURCES += ["ntt_e256t_fused.hip"]  # the two-pass single launch on 4096-element tiles (2^20)
 SOURCES += [f"ntt_{e}_{k}.hip" for e in ("e384", "e256", "e256w", "ep") for k in ("col", "single", "fin", "misc")]
+SOURCES += [f"ntt_{e}_lde.hip" for e in ("e384", "e256", "e256w", "ep", "eg", "e31")]  # low-degree-extension first passes (ntt_lde_batch)
 SOURCES += ["ntt_e256_stk.hip", "ntt_ep_stk.hip"]  # the bellperson-family rival schedule (NTT_PLAN_STOCKHAM)
 SOURCES += ["ntt_e256_dit.hip", "ntt_ep_dit.hip"]  # the GZKP(B, G) rival schedule (NTT_PLAN_GZKP)
 SOURCES += ["ntt_e256_rows.hip", "ntt_e256w_rows.hip", "ntt_ep_rows.hip"]  # batched single-tile transforms, several per workgroup (KIND_ROWS)

@@ -82,6 +82,13 @@ template <>
 struct HasRows<Eng31> {  // primes below 2^31 on 4-B elements, ntt_e31_rows.hip
   static constexpr bool value = true;
 };
+// engines with low-degree-extension instances (PRO_LDE first passes, ntt_*_lde.hip): every engine a
+// default plan runs on; not the NTT_PLAN_IN_PLACE engines nor the 4096-element tiles
+template <class E>
+struct HasLde {
+  static constexpr bool value = std::is_same_v<E, Eng256> || std::is_same_v<E, Eng384> || std::is_same_v<E, Eng256w> ||
+                                std::is_same_v<E, EngP> || std::is_same_v<E, Eng64G> || std::is_same_v<E, Eng31>;
+};
 
 // a modulus as W little-endian 32-bit words (canonical-range checks)
 template <int W>
@@ -126,7 +133,9 @@ struct PassArgs {
   const uint32_t* tw_hi;
   const uint32_t* tw_full;  // column pass: per-pass outer twiddle table (HBM element format) or null
   const uint32_t* src2;     // first column pass of a fused polymul inverse: x <- mont(src, src2) at load
-  const uint32_t* tw_in;    // first column pass of a fused coset forward: x_d <- x_d u^d (Shoup table, d < R)
+  const uint32_t* tw_in;    // first column pass of a fused coset forward: x_d <- x_d u^d (Shoup table, d < R);
+                            // PRO_LDE without a full table, where lde_mul_at_load(): the shift's two-level
+                            // lo_s table (null: no shift, or the inputs are already scaled)
   uint32_t lo_bits;
   uint32_t log_n;
   uint32_t log_blk;  // column pass: log2 of the block length N_i
@@ -169,6 +178,11 @@ struct PassArgs {
   // debug builds (NTT_DEBUG_CHECKS): element extents of src / dst from this transform's first element
   // (~0: not checked, e.g. four-step maps into the caller's exchange blocks)
   size_t dbg_src_n, dbg_dst_n;
+  // ---- low-degree extension (PRO_LDE, ntt_lde_batch): the pass that reads the caller's buffer takes
+  // transform b's input at src + b src_stride, src_stride / E::MEMW elements long; positions at and
+  // above that length are zero and never loaded (batch_stride stays the destination's stride)
+  size_t src_stride;        // 32-bit words between the batch's inputs (n_in * E::MEMW)
+  const uint32_t* tw_in_hi; // the shift's two-level hi table (with tw_in = lo_s: c^j at load)
 };
 enum : uint32_t { FS_MAP_IN = 1u, FS_MAP_OUT = 2u, FS_IL = 4u, FS_MAP_EPI = 8u };
 
@@ -237,6 +251,37 @@ hipError_t launch_pass_kind(int logr, const uint32_t* src, uint32_t* dst, const 
 template <class E>
 hipError_t launch_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
                        uint32_t batch, hipStream_t st);
+// PRO_LDE passes without the shift in their outer table: is the two-level product c^j = lo_s * hi
+// compiled in at the load?  Yes on the one- and two-word engines; on the 9-limb engines in
+// KIND_SINGLE only; never on the 14-limb engine.  Elsewhere the two table entries and their product
+// do not fit beside the tile (the pass would spill where its plain sibling does not), and
+// the shift is applied by launch_lde_scale over the inputs first.
+template <class E, int KIND>
+__host__ __device__ constexpr bool lde_mul_at_load() {
+  return E::W <= 2 || (E::W <= 9 && KIND == KIND_SINGLE);
+}
+// PRO_LDE instances that exist.  A few passes that sit at their register cap spill with the padded
+// load where their plain sibling does not: the 14-limb engine's radix-8 column pass and its
+// 8- and 16-point single tiles, and the 9-limb engines' radix-64 column pass in the generic (non-FAST)
+// form.  They are not instantiated; ntt_lde_batch runs such a plan through the zero-padded staging
+// route (PlanImpl::lde_staged).  fast: the FAST form (A.F.red_ok on a fast-reduction engine).
+template <class E>
+__host__ __device__ constexpr bool lde_pass_available(int kind, int logr, bool fast) {
+  if (E::W > 9) return !((kind == KIND_COLUMN && logr == 3) || (kind == KIND_SINGLE && logr <= 4));
+  if (E::W == 9) return !(kind == KIND_COLUMN && logr == 6 && !fast);
+  return true;
+}
+// dst[v n_in + j] = src[v n_in + j] c^j (j < n_in, v < batch; canonical in and out), c^j from the
+// shift's two-level tables: the inputs of a low-degree extension whose first pass cannot take the
+// product at load.  Engines with HasLde only.
+template <class E>
+hipError_t launch_lde_scale(const uint32_t* src, uint32_t* dst, size_t n_in, uint32_t batch, const uint32_t* lo_s,
+                            const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F, hipStream_t st);
+// The pass of a low-degree extension that reads the caller's buffer (PRO_LDE): kind = KIND_COLUMN (the
+// first pass of a multi-pass size) or KIND_SINGLE (sizes up to one tile).  Engines with HasLde only.
+template <class E>
+hipError_t launch_lde_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
+                           uint32_t batch, hipStream_t st);
 template <class E>
 hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,
                            const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F,

@@ -288,7 +288,14 @@ __device__ __forceinline__ void substage(uint32_t (&x)[E::EPT][E::W], uint32_t (
 //   PRO_COSET: coset forward, x_j <- x_j c^j with j = col + s d: x_j u^d (u = c^s, Shoup table
 //              A.tw_in over the in-column index d) and c^col folded into the outer-twiddle table
 //              (PlanImpl::coset).
-enum : int { PRO_NONE = 0, PRO_PW = 1, PRO_COSET = 2 };
+//   PRO_LDE:   low-degree extension (ntt_lde_batch), in the pass that reads the caller's buffer (the
+//              first column pass, or KIND_SINGLE).  Transform b's input is the A.src_stride / MEMW
+//              coefficients at src + b A.src_stride; a position at or above that length is the
+//              engine's zero and is not loaded.  The shift's c^j rides at load: with a full table the
+//              PRO_COSET way (u^d here, c^col in the table), else from the two-level tables
+//              A.tw_in (lo_s) and A.tw_in_hi as k_scale_pow does (A.tw_in null: no shift), where
+//              lde_mul_at_load(); the other passes read inputs that k_lde_scale has scaled.
+enum : int { PRO_NONE = 0, PRO_PW = 1, PRO_COSET = 2, PRO_LDE = 3 };
 // FSM: four-step addressing (PassArgs::fs) compiled in: 0 = plain batched transforms (every
 // product path), 1 = chunk maps / interleave, 2 = the same plus the output twiddle epilogue.
 // SHTW: the column pass's full outer-twiddle table holds Shoup pairs (PassArgs::tw_sh).
@@ -513,7 +520,8 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
   const bool single_il = (KIND == KIND_SINGLE || ROWS) && fs_il;
   const size_t tstride = A.batch_stride / E::MEMW;  // elements between batched transforms
   const size_t bidx = (size_t)bq * tstride;         // first element of this transform (KIND_ROWS: bq = 0)
-  if (!map_in && !single_il) src += bidx * SW;
+  if constexpr (PRO == PRO_LDE) src += (size_t)bq * A.src_stride;  // the inputs are shorter than the outputs
+  else if (!map_in && !single_il) src += bidx * SW;
   if (!map_out && !single_il) dst += bidx * DW;
   const size_t boff = bidx * E::MEMW;  // caller-buffer words (src2)
   // input element `pos` of transform b (= bq, or w T + c in KIND_ROWS; Mode I column passes: the
@@ -630,14 +638,46 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
           pos = pi;
         }
         const size_t b = ROWS ? (size_t)w * T + c : (size_t)bq;  // this element's transform
-        E::template load<SW>(x[j * Q + d], src, ck(IN_USER ? in_pos(pos, b) : pos, A.dbg_src_n));
+        if constexpr (PRO == PRO_LDE) {
+          static_assert(FSM == 0 && SRC_USER && (KIND == KIND_SINGLE || KIND == KIND_COLUMN), "PRO_LDE passes");
+          // pos is the position in the transform (pass 1 has one block).  Zeros past the input's end
+          // come from registers; a tile with no input at all still runs and stores its zeros over
+          // whatever the scratch or the caller's buffer held.
+          if (pos < A.src_stride / E::MEMW) {
+            E::template load<SW>(x[j * Q + d], src, ck(pos, A.dbg_src_n));
 #if NTT_DEBUG_CHECKS
-        // the caller's elements must be canonical (the reference's BAD LIMB trap); a column pass reads
-        // them only when A.src_user (one SRC_USER instance also serves later passes when the scratch
-        // and caller layouts agree)
-        if (KIND == KIND_SINGLE || ROWS || (KIND == KIND_COLUMN && A.src_user))
-          if (!E::dbg_canonical(x[j * Q + d], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
+            if (!E::dbg_canonical(x[j * Q + d], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
 #endif
+            if constexpr (KIND == KIND_COLUMN && FULLTW) {
+              if (A.tw_in) {  // c^pos = c^col (outer table) u^pi; null: no shift, the plan's own table
+                typename E::Tw u;
+                E::tload(u, A.tw_in, pi);
+                E::mul(x[j * Q + d], u, A.F);  // < 3p, normalised
+              }
+            } else if constexpr (lde_mul_at_load<E, KIND>()) {
+              if (A.tw_in) {  // c^pos = lo_s[pos mod 2^lo_bits] hi[pos >> lo_bits]
+                typename E::Tw tl, th;
+                E::tload(tl, A.tw_in, (uint32_t)(pos & ((1u << A.lo_bits) - 1)));
+                E::tload(th, A.tw_in_hi, (uint32_t)(pos >> A.lo_bits));
+                E::mul(tl.w, th, A.F);
+                E::mulv(x[j * Q + d], tl.w, A.F);
+              }
+            }
+          } else {
+#pragma unroll
+            for (int l = 0; l < E::W; ++l) x[j * Q + d][l] = 0u;
+          }
+        } else {
+          E::template load<SW>(x[j * Q + d], src, ck(IN_USER ? in_pos(pos, b) : pos, A.dbg_src_n));
+#if NTT_DEBUG_CHECKS
+          // the caller's elements must be canonical (the reference's BAD LIMB trap); a column pass reads
+          // them only when A.src_user (one SRC_USER instance also serves later passes when the scratch
+          // and caller layouts agree)
+          if (KIND == KIND_SINGLE || ROWS || (KIND == KIND_COLUMN && A.src_user)) {
+            if (!E::dbg_canonical(x[j * Q + d], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
+          }
+#endif
+        }
         if constexpr ((KIND == KIND_STOCKHAM || KIND == KIND_DIT) && FULLTW) {
           // bellperson's input twiddle (GZKP-NTT.cu:348-354): element pi of group k = index mod p is
           // multiplied by w_n^((n >> lgp >> deg) k pi), from a [k / T][pi][k mod T] table (p >= T).
@@ -2249,6 +2289,101 @@ hipError_t launch_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, c
   return launch_pass_kind<E, KIND_SINGLE>(logr, src, dst, A, grid, batch, st);
 }
 
+// The PRO_LDE pass (low-degree extension, ntt_lde_batch): one outer-table form per engine.  Fast-
+// reduction engines on a modulus that takes them (A.F.red_ok) run the column pass with the shift's
+// full table (A.tw_full and A.tw_in, as PRO_COSET) and KIND_SINGLE in the FAST form; every other case
+// the generic reductions with two-level outer twiddles.
+template <class E, int KIND, int LOGR>
+static hipError_t launch_lde_r(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid, uint32_t batch,
+                               hipStream_t st) {
+  constexpr int TL = tile_log_of<E>();
+  constexpr int MAXR = (KIND == KIND_SINGLE) ? TL : TL - E::MIN_COLS_LOG;
+  if constexpr (LOGR > MAXR || !HasLde<E>::value) {
+    return hipErrorInvalidValue;
+  } else {
+    constexpr int TE = (KIND == KIND_SINGLE) ? (1 << LOGR) : (1 << TL);
+    constexpr int NT = TE / E::EPT;
+    const dim3 g(grid, batch), b(NT < 64 ? 64 : NT);
+    if (A.fs || A.tw_epi || A.src2 || A.tw_sh || A.src_stride == 0) return hipErrorInvalidValue;
+    if constexpr (E::FASTRED) {
+      if (A.F.red_ok) {
+        // a plan's passes are all FAST or all generic: no generic column pass beside FAST later ones
+        // (a FAST plan without full tables takes the staging route instead)
+        if constexpr (KIND == KIND_COLUMN) {
+          if (!A.tw_full) return hipErrorInvalidValue;
+          hipLaunchKernelGGL((k_pass<E, LOGR, KIND_COLUMN, true, true, PRO_LDE>), g, b, 0, st, src, dst, A);
+        } else {
+          hipLaunchKernelGGL((k_pass<E, LOGR, KIND_SINGLE, false, true, PRO_LDE>), g, b, 0, st, src, dst, A);
+        }
+        return hipGetLastError();
+      }
+    }
+    if (A.tw_full || (A.tw_in && !lde_mul_at_load<E, KIND>())) return hipErrorInvalidValue;
+    if constexpr (!lde_pass_available<E>(KIND, LOGR, false)) {
+      return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((k_pass<E, LOGR, KIND, false, false, PRO_LDE>), g, b, 0, st, src, dst, A);
+      return hipGetLastError();
+    }
+  }
+}
+
+template <class E, int KIND>
+static hipError_t launch_lde_kind(int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
+                                  uint32_t batch, hipStream_t st) {
+  switch (logr) {
+    case 3: return launch_lde_r<E, KIND, 3>(src, dst, A, grid, batch, st);
+    case 4: return launch_lde_r<E, KIND, 4>(src, dst, A, grid, batch, st);
+    case 5: return launch_lde_r<E, KIND, 5>(src, dst, A, grid, batch, st);
+    case 6: return launch_lde_r<E, KIND, 6>(src, dst, A, grid, batch, st);
+    case 7: return launch_lde_r<E, KIND, 7>(src, dst, A, grid, batch, st);
+    case 8: return launch_lde_r<E, KIND, 8>(src, dst, A, grid, batch, st);
+    case 9: return launch_lde_r<E, KIND, 9>(src, dst, A, grid, batch, st);
+    case 10: return launch_lde_r<E, KIND, 10>(src, dst, A, grid, batch, st);
+    case 11: return launch_lde_r<E, KIND, 11>(src, dst, A, grid, batch, st);
+    case 12: return launch_lde_r<E, KIND, 12>(src, dst, A, grid, batch, st);
+    case 13: return launch_lde_r<E, KIND, 13>(src, dst, A, grid, batch, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The inputs of a low-degree extension times c^j, into a staging buffer of the same layout
+// (launch_lde_scale, ntt_kernels.hpp); input v is blockIdx.y
+template <class E>
+__global__ void k_lde_scale(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t n_in,
+                            const uint32_t* __restrict__ lo_s, const uint32_t* __restrict__ hi, uint32_t lo_bits,
+                            const typename E::Args F) {
+  NTT_GRID_STRIDE(j, n_in) {
+    const size_t i = (size_t)blockIdx.y * n_in + j;
+    uint32_t x[E::W];
+    typename E::Tw w, h;
+    E::load(x, src, i);
+#if NTT_DEBUG_CHECKS
+    if (!E::dbg_canonical(x, F)) ntt_dbg_flag(F.dbg, NTT_DBG_INPUT);
+#endif
+    E::tload(w, lo_s, (uint32_t)(j & ((1ull << lo_bits) - 1)));
+    E::tload(h, hi, (uint32_t)(j >> lo_bits));
+    E::mul(w.w, h, F);
+    E::mulv(x, w.w, F);
+    E::template store<E::MUL_OUT>(dst, i, x, F);
+  }
+}
+
+template <class E>
+hipError_t launch_lde_scale(const uint32_t* src, uint32_t* dst, size_t n_in, uint32_t batch, const uint32_t* lo_s,
+                            const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F, hipStream_t st) {
+  hipLaunchKernelGGL((k_lde_scale<E>), dim3(grid_1d(n_in), batch), dim3(256), 0, st, src, dst, n_in, lo_s, hi, lo_bits, F);
+  return hipGetLastError();
+}
+
+template <class E>
+hipError_t launch_lde_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
+                           uint32_t batch, hipStream_t st) {
+  if (kind == KIND_COLUMN) return launch_lde_kind<E, KIND_COLUMN>(logr, src, dst, A, grid, batch, st);
+  if (kind == KIND_SINGLE) return launch_lde_kind<E, KIND_SINGLE>(logr, src, dst, A, grid, batch, st);
+  return hipErrorInvalidValue;
+}
+
 template <class E>
 hipError_t launch_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t batch, hipStream_t st) {
   hipLaunchKernelGGL((k_dft_naive<E>), dim3(1, batch), dim3(64), 0, st, src, dst, A);
@@ -2285,7 +2420,14 @@ hipError_t launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* c, s
   extern template hipError_t launch_pass_kind<E, KIND>(int, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
                                                        uint32_t, hipStream_t);
 
-#define NTT_INSTANTIATE_FUSED(E)                                                                                  \
+// The PRO_LDE passes of one engine (a translation unit of their own: ntt_*_lde.hip)
+#define NTT_INSTANTIATE_LDE(E)                                                                                  \
+  template hipError_t launch_lde_pass<E>(int, int, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
+                                         uint32_t, hipStream_t);                                             \
+  template hipError_t launch_lde_scale<E>(const uint32_t*, uint32_t*, size_t, uint32_t, const uint32_t*,       \
+                                          const uint32_t*, uint32_t, const typename E::Args&, hipStream_t);
+
+#define NTT_INSTANTIATE_FUSED(E)                                                                                 \
   template hipError_t launch_fused3<E>(int, int, int, const uint32_t*, uint32_t*, uint32_t*, const PassArgs<E>&,     \
                                        const PassArgs<E>&, const PassArgs<E>&, const FusedArgs&, hipStream_t);      \
   template hipError_t fused3_capacity<E>(int, int, int, int, uint32_t*, uint32_t);

@@ -36,6 +36,19 @@ namespace {
 
 thread_local int g_last_error = NTT_OK;
 
+// A low-degree extension through run_io (PlanImpl::lde): the inputs' length and, where the shift is
+// not folded into the first pass's outer table, its two-level tables (null: no shift)
+struct LdeIO {
+  size_t n_in = 0;
+  const uint32_t* lo = nullptr;
+  const uint32_t* hi = nullptr;
+  // the engines without the product at load: the inputs are first scaled into `stage` (launch_lde_scale
+  // with these two-level tables), which the first pass then reads
+  const uint32_t* scale_lo = nullptr;
+  const uint32_t* scale_hi = nullptr;
+  uint32_t* stage = nullptr;
+};
+
 // the bealto-family rival schedules (ntt.h): one k_bealto variant each
 constexpr unsigned kBealtoFlags = NTT_PLAN_BELLPERSON | NTT_PLAN_IMPROVED_V1 | NTT_PLAN_IMPROVED_V2 |
                                   NTT_PLAN_IMPROVED_V3 | NTT_PLAN_IMPROVED_V4;
@@ -208,6 +221,9 @@ struct PlanBase {
   virtual unsigned passes_for(unsigned log_x) const = 0;
   virtual unsigned max_radix_for(unsigned log_x) const = 0;
   virtual int coset(void* d, const uint64_t* shift, unsigned limbs64, bool inverse, hipStream_t st) = 0;
+  // low-degree extension (ntt_lde_batch): batch inputs of n >> log_blowup coefficients to batch outputs of n
+  virtual int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* shift, unsigned limbs64,
+                  unsigned batch, hipStream_t st) = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -642,6 +658,7 @@ struct PlanImpl final : PlanBase {
     if (d_bad) (void)hipFree(d_bad);
     if (d_coset) (void)hipFree(d_coset);
     if (d_coset_full) (void)hipFree(d_coset_full);
+    if (d_lde_stage) (void)hipFree(d_lde_stage);
     if (d_sync) (void)hipFree(d_sync);
     if (d_sync_ip) (void)hipFree(d_sync_ip);
     if (d_sync2) (void)hipFree(d_sync2);
@@ -1209,6 +1226,8 @@ struct PlanImpl final : PlanBase {
   uint32_t* d_coset_full = nullptr;  // fused coset forward: pass-1 outer twiddles x c^col (n entries)
   bool coset_full_ok = false;
   size_t coset_off[2][3] = {};  // [dir][lo_s, hi, u^d (forward only)] word offsets into d_coset
+  uint32_t* d_lde_stage = nullptr;  // ntt_lde_batch: scaled inputs of the engines without the product at load
+  size_t lde_stage_elems = 0;
   std::vector<uint32_t> pm2_;    // p - 2 (inversion exponent)
 
   unsigned long long* d_bad = nullptr;  // canonical-range check counter
@@ -1230,8 +1249,8 @@ struct PlanImpl final : PlanBase {
     return NTT_OK;
   }
 
-  int coset(void* d, const uint64_t* shift, unsigned limbs64, bool inverse, hipStream_t st) override {
-    if (!d || !shift || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
+  // The cached c^j tables (d_coset) of `shift`: checked (canonical, nonzero) and rebuilt when it changed
+  int ensure_coset_tables(const uint64_t* shift, unsigned limbs64) {
     Vec<NH> c{};
     // (the host words may reach past the caller's limbs: Goldilocks, NH = 3 over one 64-bit limb)
     for (int i = 0; i < NH && (unsigned)(i / 2) < limbs64; ++i) c[i] = (uint32_t)(shift[i / 2] >> (32 * (i % 2)));
@@ -1262,6 +1281,12 @@ struct PlanImpl final : PlanBase {
       if (hipMemcpy(d_coset, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTT_ERR_HIP;
       coset_key = key;
     }
+    return NTT_OK;
+  }
+
+  int coset(void* d, const uint64_t* shift, unsigned limbs64, bool inverse, hipStream_t st) override {
+    if (!d || !shift || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
+    if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
     const int dir = inverse ? 1 : 0;
     auto scale = [&]() {
       return launch_scale_pow<E>(static_cast<uint32_t*>(d), log_n, 1, d_coset + coset_off[dir][0],
@@ -1280,6 +1305,89 @@ struct PlanImpl final : PlanBase {
     }
     if (int rc = run(d, 1, true, st)) return rc;
     return scale();
+  }
+
+  // Low-degree extension: the first pass (PRO_LDE) reads the n_in = n >> log_blowup coefficients of
+  // each input and takes the padding from registers.  The shift's c^j is applied at that load: the
+  // fused coset's way (u^d at load, c^col in the cached outer table) where coset_fusable(), else from
+  // the shift's two-level tables where the pass has room (lde_mul_at_load), else by one launch over the
+  // inputs into the plan's staging buffer (recorded as an unlabelled launch).  Without a shift nothing
+  // of the shift cache is touched: a fusable plan's pass then takes the plan's own pass-1 table.
+  // The few passes without a PRO_LDE instance (lde_pass_available), 2- and 4-point plans, and fast-
+  // reduction plans that could not build their full tables go through lde_staged.
+  int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* shift, unsigned limbs64, unsigned batch,
+          hipStream_t st) override {
+    if constexpr (!HasLde<E>::value) {
+      return NTT_ERR_ARG;
+    } else {
+      if (!in || !out || batch == 0 || log_blowup > log_n) return NTT_ERR_ARG;
+      if (flags & (NTT_PLAN_TWIDDLE_ONLY | NTT_PLAN_IN_PLACE)) return NTT_ERR_ARG;
+      const size_t n_in = (size_t)(n >> log_blowup), eb = (size_t)MEMW * 4;
+      const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)batch * n_in * eb;
+      const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)batch * (size_t)n * eb;
+      if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // the first pass reads d_in while later tiles write d_out
+      if (shift)
+        if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
+      const uint32_t* src = static_cast<const uint32_t*>(in);
+      uint32_t* dst = static_cast<uint32_t*>(out);
+      if (log_n == 0) {  // one coefficient, one evaluation: c^0 = 1
+        if (hipMemcpyAsync(dst, src, (size_t)batch * eb, hipMemcpyDeviceToDevice, st) != hipSuccess) return NTT_ERR_HIP;
+        return NTT_OK;
+      }
+      bool fast = false;
+      if constexpr (E::FASTRED) fast = Ff.red_ok != 0;
+      const bool fuse = coset_fusable();
+      const int kind = npass == 1 ? KIND_SINGLE : KIND_COLUMN;
+      if (npass == 0 || !lde_pass_available<E>(kind, (int)r[0], fast) || (fast && npass >= 2 && !fuse))
+        return lde_staged(src, dst, n_in, shift != nullptr, batch, st);
+      LdeIO L;
+      L.n_in = n_in;
+      if (fuse) {
+        if (!shift && !d_fulls[0]) return lde_staged(src, dst, n_in, false, batch, st);
+        if (!shift)  // the plan's own pass-1 table (element format), no product at load
+          return run_io(src, nullptr, dst, batch, false, st, d_fulls[0] + full_off[0] * TABW, nullptr, nullptr, &L);
+        if (int rc = ensure_coset_full()) return rc;
+        return run_io(src, nullptr, dst, batch, false, st, d_coset_full, d_coset + coset_off[0][2], nullptr, &L);
+      }
+      if (shift) {
+        const uint32_t* lo = d_coset + coset_off[0][0];
+        const uint32_t* hi = d_coset + coset_off[0][1];
+        const bool at_load = npass == 1 ? lde_mul_at_load<E, KIND_SINGLE>() : lde_mul_at_load<E, KIND_COLUMN>();
+        if (at_load) {
+          L.lo = lo;
+          L.hi = hi;
+        } else {
+          // the multi-limb engines' first pass has no room for the two table entries: one launch over
+          // the batch n_in inputs scales them into the plan's staging buffer, which the pass then reads
+          const size_t need = (size_t)batch * n_in;
+          if (need > lde_stage_elems) {
+            if (d_lde_stage) (void)hipFree(d_lde_stage);
+            d_lde_stage = nullptr;
+            lde_stage_elems = 0;
+            if (hipMalloc(&d_lde_stage, need * eb) != hipSuccess) return NTT_ERR_HIP;
+            lde_stage_elems = need;
+          }
+          L.scale_lo = lo;
+          L.scale_hi = hi;
+          L.stage = d_lde_stage;
+        }
+      }
+      return run_io(src, nullptr, dst, batch, false, st, nullptr, nullptr, nullptr, &L);
+    }
+  }
+
+  // The zero-padded route of a low-degree extension, for the plans whose first pass has no PRO_LDE
+  // form: the padded vectors are staged in d_out (memset, strided copy), scaled by c^j there
+  // (k_scale_pow over the N-sized vectors) and transformed in place by the plan's plain forward.
+  int lde_staged(const uint32_t* src, uint32_t* dst, size_t n_in, bool shifted, unsigned batch, hipStream_t st) {
+    const size_t eb = (size_t)MEMW * 4;
+    if (hipMemsetAsync(dst, 0, (size_t)batch * (size_t)n * eb, st) != hipSuccess ||
+        hipMemcpy2DAsync(dst, (size_t)n * eb, src, n_in * eb, n_in * eb, batch, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return NTT_ERR_HIP;
+    if (shifted && launch_scale_pow<E>(dst, log_n, batch, d_coset + coset_off[0][0], d_coset + coset_off[0][1], lo_bits,
+                                       Ff, st) != hipSuccess)
+      return NTT_ERR_HIP;
+    return run_io(dst, nullptr, dst, batch, false, st);
   }
 
   bool coset_fusable() const {
@@ -1380,7 +1488,8 @@ struct PlanImpl final : PlanBase {
   // Fused coset forward: full0 replaces the first pass's outer-twiddle table and tw_in scales its
   // inputs (PRO_COSET in ntt_kernels_impl.hpp).
   int run_io(const uint32_t* in, const uint32_t* in2, uint32_t* out, unsigned batch, bool inverse, hipStream_t st,
-             const uint32_t* full0 = nullptr, const uint32_t* tw_in = nullptr, const FsIO* io = nullptr) {
+             const uint32_t* full0 = nullptr, const uint32_t* tw_in = nullptr, const FsIO* io = nullptr,
+             const LdeIO* lde = nullptr) {
     const uint32_t il = (io && (io->fs & FS_IL)) ? io->il : 0u;
     auto set_fs = [&](PassArgs<E>& A, uint32_t bits) {
       if (!io) return;
@@ -1399,6 +1508,15 @@ struct PlanImpl final : PlanBase {
     const size_t* off_int = inverse ? off_int_i : off_int_f;
     hipError_t e = hipSuccess;
     begin(st);
+    if (lde && lde->stage) {  // an interval of the call's record, unlabelled (no pass kind of its own)
+      if constexpr (HasLde<E>::value) {
+        if (launch_lde_scale<E>(in, lde->stage, lde->n_in, batch, lde->scale_lo, lde->scale_hi, lo_bits, Ff, st) !=
+            hipSuccess)
+          return NTT_ERR_HIP;
+      }
+      mark(st);
+      in = lde->stage;
+    }
     if (npass == 0) {
       PassArgs<E> A = base_args(inverse);
       A.tw_int = d_tab + off_int[0];
@@ -1412,6 +1530,19 @@ struct PlanImpl final : PlanBase {
       set_fs(A, FS_MAP_IN | FS_MAP_OUT);
       if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
       set_extents(A, io, il);
+      if (lde) {  // low-degree extension of at most one tile: one transform per workgroup
+        if constexpr (HasLde<E>::value) {
+          A.src_stride = lde->n_in * MEMW;
+          A.tw_in = lde->lo;
+          A.tw_in_hi = lde->hi;
+          A.dbg_src_n = lde->n_in;
+          e = launch_lde_pass<E>(KIND_SINGLE, (int)r[0], in, out, A, 1, batch, st);
+        } else {
+          e = hipErrorInvalidValue;
+        }
+        mark(st, "s", r[0]);
+        return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+      }
       const uint32_t nt = il ? (1u << il) : batch;  // transforms of this launch
       // KIND_ROWS: TILE / n transforms per workgroup (the final pass's block layout: wave-uniform trivial
       // twiddles, 4-wave workgroups) when the engine has it and the count divides; NTT_ROWS=0: one per
@@ -1483,6 +1614,18 @@ struct PlanImpl final : PlanBase {
           A.tw_full = full0;
           A.tw_sh = 0;
         }
+        if (i == 0 && lde) {  // PRO_LDE: short inputs; without the fused table, two-level outer twiddles
+          A.src_stride = lde->n_in * MEMW;
+          if (full0) {  // the shift's cached table with tw_in, or the plan's own pass-1 table without
+            A.tw_full = full0;
+            A.tw_sh = 0;
+          } else {
+            A.tw_full = nullptr;
+            A.tw_sh = 0;
+            A.tw_in = lde->lo;
+            A.tw_in_hi = lde->hi;
+          }
+        }
         A.log_blk = blk + il;
         A.log_m = log_n - blk;
         A.src_user = (i == 0) ? 1u : 0u;
@@ -1506,6 +1649,7 @@ struct PlanImpl final : PlanBase {
       if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
       if (inplace) A.flags |= 2u;
       for (unsigned i = 0; i < npass; ++i) set_extents(PA[i], io, il);
+      if (lde) PA[0].dbg_src_n = lde->n_in;
       // XCD-grouped tile order (k_pass flag bit 2) for the column passes after the first whose runs are
       // shorter than a 128-B line (the 8-B path's 4-B scratch at radix 512: 64-B runs), so that the
       // two tiles sharing each line meet on one XCD's L2.  Passes of one column per tile (radix 4096 on
@@ -1525,7 +1669,7 @@ struct PlanImpl final : PlanBase {
             PA[i].flags |= 4u;
         }
       if constexpr (fused2_engine<E>()) {  // 2^20 on 4096-element tiles: the two-pass single launch
-        if (!io && batch == 1 && npass == 2 && fused_enabled() && fused2_ready(PA, inplace)) {
+        if (!io && !lde && batch == 1 && npass == 2 && fused_enabled() && fused2_ready(PA, inplace)) {
           FusedArgs F = inplace ? fargs2_ip : fargs2;
           F.wd = watchdog(F.wd.abort);
           F.trace = fused_trace_buffer(F.nwg);
@@ -1553,7 +1697,7 @@ struct PlanImpl final : PlanBase {
         }
       }
       if constexpr (std::is_same_v<E, Eng256>) {  // the engine k_fused3 is instantiated for
-        if (!io && !inplace && batch == 1 && fused_enabled() && fused_ready(PA)) {
+        if (!io && !lde && !inplace && batch == 1 && fused_enabled() && fused_ready(PA)) {
           // one persistent launch for the three passes (NTT_PLAN_SINGLE_LAUNCH, k_fused3)
           FusedArgs F = fused_args();
           F.wd = watchdog(F.wd.abort);
@@ -1591,7 +1735,12 @@ struct PlanImpl final : PlanBase {
       }
       for (unsigned i = 0; i + 1 < npass && e == hipSuccess; ++i) {
         const uint32_t* src = (i == 0) ? in : work;
-        e = launch_pass<E>(KIND_COLUMN, (int)r[i], src, work, PA[i], grid, batch, st);
+        if (i == 0 && lde) {
+          if constexpr (HasLde<E>::value) e = launch_lde_pass<E>(KIND_COLUMN, (int)r[0], src, work, PA[0], grid, batch, st);
+          else e = hipErrorInvalidValue;
+        } else {
+          e = launch_pass<E>(KIND_COLUMN, (int)r[i], src, work, PA[i], grid, batch, st);
+        }
         mark(st, "c", r[i], PA[i].tw_sh != 0);
       }
       if (e == hipSuccess && inplace && batch == 1 && ipn_ready(A)) {
@@ -2330,6 +2479,16 @@ static int run_coset(ntt_plan* plan, void* d, const uint64_t* shift, bool inv, v
 }
 int ntt_forward_coset(ntt_plan* plan, void* d, const uint64_t* shift, void* s) { return run_coset(plan, d, shift, false, s); }
 int ntt_inverse_coset(ntt_plan* plan, void* d, const uint64_t* shift, void* s) { return run_coset(plan, d, shift, true, s); }
+
+// The plan's own engine on its default schedule (never the second plan of 4096-element tiles)
+int ntt_lde_batch(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
+                  unsigned batch, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    const unsigned limbs64 = P.elem_bytes >= 32 ? P.elem_bytes / 8 : 1;
+    return P.lde(d_in, d_out, log_blowup, shift, limbs64, batch, S(s));
+  });
+}
 
 int ntt_pointwise_mul(ntt_plan* plan, const void* a, const void* b, void* c, void* s) {
   return on_device(plan, [&](PlanBase& P) { return P.pointwise(a, b, c, S(s)); });

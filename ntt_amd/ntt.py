@@ -23,7 +23,7 @@ import torch
 from . import lib as _L
 from .fields import FIELDS, field_params
 
-__all__ = ["NTTPlan", "SSIP", "NTT_GZKP", "to_device", "from_device", "FIELDS"]
+__all__ = ["NTTPlan", "SSIP", "NTT_GZKP", "lde_from_evals", "to_device", "from_device", "FIELDS"]
 
 
 def _stream_ptr(stream, device) -> C.c_void_p:
@@ -225,7 +225,8 @@ class NTTPlan:
         return t
 
     def forward_coset(self, t: torch.Tensor, shift: int, stream=None) -> torch.Tensor:
-        """Evaluations on the coset shift*<w>: X_k = sum_j x_j (shift w^k)^j (low-degree extension)."""
+        """Evaluations on the coset shift*<w>: X_k = sum_j x_j (shift w^k)^j, one vector of the plan's
+        size in place (no padding, no batch: ``lde_batch`` is the low-degree extension)."""
         self._check_tensor(t)
         _L.check(self._lib.ntt_forward_coset(self._h, C.c_void_p(t.data_ptr()),
                                              _u64_array(int_to_limbs(int(shift), self.limbs64)),
@@ -239,6 +240,42 @@ class NTTPlan:
                                              _u64_array(int_to_limbs(int(shift), self.limbs64)),
                                              _stream_ptr(stream, t.device)), "ntt_inverse_coset")
         return t
+
+    def _check_lde(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int],
+                   batch: int) -> None:
+        if not isinstance(log_blowup, int) or not 0 <= log_blowup <= self.log_n:
+            raise ValueError(f"log_blowup must be an integer in [0, {self.log_n}], not {log_blowup!r}")
+        if not isinstance(batch, int) or batch < 1:
+            raise ValueError(f"batch must be a positive integer, not {batch!r}")
+        if shift is not None and not 0 < int(shift) < self.p:
+            raise ValueError("shift must be canonical and nonzero (0 < shift < p)")
+        n_in = self.n >> log_blowup
+        for t, count, what in ((coeffs, batch * n_in, "coeffs"), (out, batch * self.n, "out")):
+            if not t.is_cuda:
+                raise ValueError(f"{what} must be a device (HIP) tensor")
+            if not t.is_contiguous() or t.dtype != self.dtype:
+                raise ValueError(f"{what} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the "
+                                 "plan's element layout")
+            if t.numel() * t.element_size() != count * self.elem_bytes:
+                raise ValueError(f"{what}: expected {count} elements of {self.elem_bytes} bytes")
+            if t.device.index != self.device:
+                raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
+        a0, b0 = coeffs.data_ptr(), out.data_ptr()
+        if a0 < b0 + batch * self.n * self.elem_bytes and b0 < a0 + batch * n_in * self.elem_bytes:
+            raise ValueError("coeffs and out overlap")
+
+    def lde_batch(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int] = None,
+                  batch: int = 1, stream=None) -> torch.Tensor:
+        """Low-degree extension (ntt_lde_batch).  This plan has the LARGE size N = 2^log_n; ``coeffs``
+        holds ``batch`` polynomials of n = N >> log_blowup coefficients back to back, ``out`` receives
+        ``batch`` vectors of N evaluations: out[v][k] = sum_j coeffs[v][j] (shift w_N^k)^j (shift None: 1).
+        ``coeffs`` is not modified and must not overlap ``out``."""
+        self._check_lde(coeffs, out, log_blowup, shift, batch)
+        sh = None if shift is None else _u64_array(int_to_limbs(int(shift), self.limbs64))
+        _L.check(self._lib.ntt_lde_batch(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
+                                         int(log_blowup), sh, int(batch), _stream_ptr(stream, out.device)),
+                 "ntt_lde_batch")
+        return out
 
     def pointwise_mul(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, stream=None) -> torch.Tensor:
         for t in (a, b, out):
@@ -336,6 +373,21 @@ class NTTPlan:
             self.close()
         except Exception:
             pass
+
+
+def lde_from_evals(small_plan: NTTPlan, big_plan: NTTPlan, evals: torch.Tensor, out: torch.Tensor,
+                   shift: Optional[int] = None, batch: int = 1, stream=None) -> torch.Tensor:
+    """Evaluations of ``batch`` polynomials on <w_n> (``small_plan``'s size) -> their evaluations on the
+    coset shift*<w_N> (``big_plan``'s size): ``small_plan.inverse_batch`` followed by
+    ``big_plan.lde_batch``.  The inverse overwrites ``evals`` with the coefficients."""
+    if big_plan.log_n < small_plan.log_n:
+        raise ValueError("big_plan must be at least as large as small_plan")
+    if (small_plan.p, small_plan.limbs64, small_plan.elem_bytes, small_plan.montgomery_io) != \
+            (big_plan.p, big_plan.limbs64, big_plan.elem_bytes, big_plan.montgomery_io):
+        raise ValueError("the two plans must share field, element layout and Montgomery-I/O mode")
+    big_plan._check_lde(evals, out, big_plan.log_n - small_plan.log_n, shift, batch)
+    small_plan.inverse_batch(evals, batch, stream=stream)
+    return big_plan.lde_batch(evals, out, big_plan.log_n - small_plan.log_n, shift, batch, stream=stream)
 
 
 # ------------------------------------------------------------------------------------ shims
