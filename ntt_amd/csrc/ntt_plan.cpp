@@ -29,6 +29,11 @@
 #include "eng29_args.hpp"
 #include "ntt_internal.hpp"
 #include "ntt_kernels.hpp"
+#include "plan_devmem.hpp"    // the plan's own parts, included here alone: DevBuf, Lazy, the watchdog-word pool
+#include "plan_hostmath.hpp"  // HostField, EngHost<E>
+#include "plan_knobs.hpp"     // every environment variable, as knob::name()
+#include "plan_rivals.hpp"    // Rivals<E, Plan>: the rival schedules
+#include "plan_schedule.hpp"  // schedule_for, schedule_palindrome
 
 using namespace ntt;
 
@@ -49,158 +54,18 @@ struct LdeIO {
   uint32_t* stage = nullptr;
 };
 
-// the bealto-family rival schedules (ntt.h): one k_bealto variant each
-constexpr unsigned kBealtoFlags = NTT_PLAN_BELLPERSON | NTT_PLAN_IMPROVED_V1 | NTT_PLAN_IMPROVED_V2 |
-                                  NTT_PLAN_IMPROVED_V3 | NTT_PLAN_IMPROVED_V4;
-
-// ------------------------------------------------------------------------------ single-launch order
-// The single launches (k_fused3 / k_fused3b / k_fused3bi / k_fused2b / k_fused2bi) wait across
-// workgroups, so each assumes its workgroups own the device: two of them enqueued on two streams could
-// have their workgroups dispatched interleaved, each holding part of the CUs, and both would wait for
-// the other's workgroups until the watchdog gave up (NTT_ERR_DEVICE).  The library therefore orders
-// them per device, under one lock: a single launch on another stream than the device's previous one
-// first makes its stream wait for everything enqueued so far on that previous stream (an event
-// recorded there at this moment), which includes the previous single launch.  Launches on one stream
-// are in order already and pay nothing: an event recorded after every launch cost 4.5 us of device time
-// per call (a marker packet behind the kernel; profiles/r06_c2/).  A previous stream that has been
-// destroyed (hipStreamGetFlags fails) has finished its work.  Work of other kinds is not ordered.
-// (The in-place forms also check residency before their first store, for CUs held by anything else:
-// ntt_kernels_impl.hpp residency_wait.)
-class FusedSerial {
- public:
-  FusedSerial(int device, hipStream_t st) : lk_(mu()), s_(enabled() ? slot(device) : nullptr), st_(st) {
-    if (!s_ || !s_->used || s_->last == st) return;
-    unsigned fl = 0;
-    if (hipStreamGetFlags(s_->last, &fl) != hipSuccess) {  // gone: its work is done
-      (void)hipGetLastError();
-      return;
-    }
-    if (!s_->ev && hipEventCreateWithFlags(&s_->ev, hipEventDisableTiming) != hipSuccess) {
-      s_->ev = nullptr;
-      (void)hipGetLastError();
-      return;
-    }
-    if (hipEventRecord(s_->ev, s_->last) == hipSuccess) (void)hipStreamWaitEvent(st, s_->ev, 0);
-  }
-  void done(hipError_t launched) {
-    if (!s_ || launched != hipSuccess) return;
-    s_->last = st_;
-    s_->used = true;
-  }
-
- private:
-  struct Slot {
-    hipStream_t last = nullptr;  // the stream of the device's latest single launch
-    bool used = false;
-    hipEvent_t ev = nullptr;     // process-lifetime, like the plan cache
-  };
-  static bool enabled() {  // NTT_FUSED_ORDER=0: no ordering (A/B only)
-    static const bool on = [] {
-      const char* v = getenv("NTT_FUSED_ORDER");
-      return !(v && *v == '0');
-    }();
-    return on;
-  }
-  static std::mutex& mu() {
-    static std::mutex* m = new std::mutex;
-    return *m;
-  }
-  static Slot* slot(int device) {
-    static Slot* slots = new Slot[64];
-    return (device >= 0 && device < 64) ? &slots[device] : nullptr;
-  }
-  std::lock_guard<std::mutex> lk_;
-  Slot* s_;
-  hipStream_t st_;
-};
-
-// Diagnostics (NTT_FUSED_TRACE=<file>): the two-pass single launch writes per-workgroup wall-clock
-// stamps (start, after pass 1, after the barrier, end; 100 MHz), appended to <file> after each call,
-// which then synchronises its stream.  Never on in measured runs.
-static const char* fused_trace_path() {
-  static const char* p = getenv("NTT_FUSED_TRACE");
-  return (p && *p) ? p : nullptr;
-}
-
-// ------------------------------------------------------------------------------ host field math
-template <int N>
-using Vec = std::array<uint32_t, N>;
-
-template <int N>
-struct HostField {
-  Modulus<N> M;
-  Vec<N> r1{}, r2{};  // R mod p, R^2 mod p
-
-  Vec<N> mul(const Vec<N>& a, const Vec<N>& b) const {
-    Vec<N> r;
-    mont_mul_cios<N>(r.data(), a.data(), b.data(), M);
-    return r;
-  }
-  Vec<N> add(const Vec<N>& a, const Vec<N>& b) const {
-    Vec<N> r;
-    add_mod<N>(r.data(), a.data(), b.data(), M);
-    return r;
-  }
-  Vec<N> to_mont(const Vec<N>& a) const { return mul(a, r2); }
-  Vec<N> from_mont(const Vec<N>& a) const {
-    Vec<N> one{};
-    one[0] = 1;
-    return mul(a, one);
-  }
-  // base (Montgomery) ^ e, e given as 32-bit little-endian words
-  Vec<N> pow(const Vec<N>& base, const std::vector<uint32_t>& e) const {
-    Vec<N> acc = r1, b = base;
-    for (size_t i = 0; i < e.size() * 32; ++i) {
-      if ((e[i / 32] >> (i % 32)) & 1) acc = mul(acc, b);
-      b = mul(b, b);
-    }
-    return acc;
-  }
-  Vec<N> pow_u64(const Vec<N>& base, uint64_t e) const {
-    return pow(base, std::vector<uint32_t>{(uint32_t)e, (uint32_t)(e >> 32)});
-  }
-};
-
-template <int N>
-static bool vec_lt(const Vec<N>& a, const Vec<N>& b) {
-  for (int i = N - 1; i >= 0; --i)
-    if (a[i] != b[i]) return a[i] < b[i];
-  return false;
-}
-
-// ------------------------------------------------------------------------------ watchdog words
-// One 4-KiB mapped, coherent pinned page per 1024 plans that use inter-workgroup waits; a plan takes
-// a 4-byte slot when it first builds such a schedule and returns it when destroyed.  The pages are
-// never freed: nothing is released during process teardown, where the HIP runtime (and a profiler
-// such as rocprofv3) may already be gone.
-static std::mutex g_watch_mu;
-static std::vector<uint32_t*> g_watch_free;
-static uint32_t* watch_slot_acquire() {
-  std::lock_guard<std::mutex> lk(g_watch_mu);
-  if (g_watch_free.empty()) {
-    void* page = nullptr;
-    if (hipHostMalloc(&page, 4096, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess)
-      return nullptr;
-    auto* w = static_cast<uint32_t*>(page);
-    for (int i = 1023; i >= 0; --i) {
-      w[i] = 0u;
-      g_watch_free.push_back(w + i);
-    }
-  }
-  uint32_t* s = g_watch_free.back();
-  g_watch_free.pop_back();
-  *s = 0u;
-  return s;
-}
-static void watch_slot_release(uint32_t* s) {
-  if (!s) return;
-  std::lock_guard<std::mutex> lk(g_watch_mu);
-  g_watch_free.push_back(s);
-}
-
 // ------------------------------------------------------------------------------ plan
 struct PlanBase {
-  virtual ~PlanBase() = default;
+  // Destruction: ~PlanImpl makes the plan's device current, its DevBuf members free themselves there,
+  // and this, which runs last, returns the watchdog slot and the events and restores the caller's device
+  virtual ~PlanBase() {
+    watch_slot_release(h_watch);
+    for (auto& row : ev)
+      for (auto& e : row)
+        if (e) (void)hipEventDestroy(e);
+    if (caller_device >= 0) (void)hipSetDevice(caller_device);
+  }
+  int caller_device = -1;  // set by ~PlanImpl
   virtual int run(void* d, unsigned batch, bool inverse, hipStream_t st) = 0;
   virtual int pointwise(const void* a, const void* b, void* c, hipStream_t st) = 0;
   virtual int polymul(void* a, void* b, void* c, hipStream_t st) = 0;
@@ -300,301 +165,14 @@ bool PlanBase::alloc_watch() {
   return true;
 }
 
-// radices for log_n: near-equal split with each radix <= tile_log - min_cols_log so that every
-// global access is a contiguous run of T = TILE / R >= 2^min_cols_log elements (>= 128 B).
-// The pass kernels also need every column pass's block to span a whole tile (N_i = R_i ... R_p >=
-// TILE, so a workgroup's T columns lie in one block) and the final pass's T blocks to fit in R_1
-// (r_1 + r_p >= tile_log).  The near-equal split violates that only for short 3-pass schedules of
-// big tiles (2^19 on the 8192-element P tiles: 7+6+6); ascending order fixes every such case.
-static bool schedule_ok(const unsigned* r, unsigned p, unsigned tile_log) {
-  if (p < 2) return true;
-  if (r[0] + r[p - 1] < tile_log) return false;
-  unsigned tail = r[p - 1];
-  for (int i = (int)p - 2; i >= 0; --i) {
-    tail += r[i];
-    if (tail < tile_log) return false;
-  }
-  return true;
-}
-// narrow_first (HBM-bound engines): pass 1, whose columns are n / R_1 elements apart, takes a radix
-// one below the rest so that its workgroups read twice as wide runs (2^24 P: 7+8+9 instead of 8+8+8).
-// NTT_SCHEDULE="r1,r2,..." (experiments only): that radix sequence for the sizes it sums to, when the
-// pass kernels accept it.
-static bool schedule_env(unsigned log_n, unsigned tile_log, unsigned rmax, unsigned* r, unsigned& p) {
-  const char* v = getenv("NTT_SCHEDULE");
-  if (!v || !*v) return false;
-  unsigned rr[8], pp = 0, sum = 0;
-  for (const char* c = v; *c && pp < 8;) {
-    const unsigned x = (unsigned)strtoul(c, const_cast<char**>(&c), 10);
-    if (x < 3 || x > rmax) return false;
-    rr[pp++] = x;
-    sum += x;
-    if (*c == ',') ++c;
-    else if (*c) return false;
-  }
-  if (sum != log_n || pp < 2 || !schedule_ok(rr, pp, tile_log)) return false;
-  for (unsigned i = 0; i < pp; ++i) r[i] = rr[i];
-  p = pp;
-  return true;
-}
-static bool schedule(unsigned log_n, unsigned tile_log, unsigned min_cols_log, bool narrow_first, unsigned* r,
-                     unsigned& p) {
-  if (log_n <= 2) { p = 0; return true; }
-  if (log_n <= tile_log) { p = 1; r[0] = log_n; return true; }
-  if (schedule_env(log_n, tile_log, tile_log - min_cols_log, r, p)) return true;
-  const unsigned rmax = tile_log - min_cols_log;
-  p = (log_n + rmax - 1) / rmax;
-  if (p < 2) p = 2;
-  const unsigned base = log_n / p, rem = log_n % p;
-  for (unsigned i = 0; i < p; ++i) r[i] = base + (i < rem ? 1 : 0);
-  if (narrow_first) {
-    std::sort(r, r + p);
-    if (r[p - 1] < rmax && r[0] > 3) {
-      r[0] -= 1;
-      r[p - 1] += 1;
-      std::sort(r + 1, r + p);
-      if (!schedule_ok(r, p, tile_log)) { r[0] += 1; r[p - 1] -= 1; std::sort(r, r + p); }
-    }
-  }
-  if (!schedule_ok(r, p, tile_log)) std::sort(r, r + p);
-  if (schedule_ok(r, p, tile_log)) return true;
-  // Neither split passes (4096-element tiles with radices <= 2^8 at 2^17: 5+6+6 has r_1 + r_p = 11):
-  // the ascending sequence of p radices in [3, rmax] that does, with the smallest largest radix, then
-  // the largest smallest one (2^17: 5+5+7).
-  unsigned best[8] = {0}, v[8] = {0}, bmax = 99, bmin = 0;
-  for (unsigned i = 0; i < p; ++i) v[i] = 3;
-  for (;;) {
-    unsigned sum = 0;
-    for (unsigned i = 0; i < p; ++i) sum += v[i];
-    if (sum == log_n && schedule_ok(v, p, tile_log) && (v[p - 1] < bmax || (v[p - 1] == bmax && v[0] > bmin))) {
-      bmax = v[p - 1];
-      bmin = v[0];
-      for (unsigned i = 0; i < p; ++i) best[i] = v[i];
-    }
-    int k = (int)p - 1;  // next non-decreasing sequence
-    while (k >= 0 && v[k] == rmax) --k;
-    if (k < 0) break;
-    ++v[k];
-    for (unsigned i = k + 1; i < p; ++i) v[i] = v[k];
-  }
-  if (bmax == 99) return false;
-  for (unsigned i = 0; i < p; ++i) r[i] = best[i];
-  return true;
-}
-
-// The schedule of an engine: schedule() at the engine's MIN_COLS_LOG (the narrowest column group its
-// kernels are instantiated for).  An engine may name a wider group it prefers (PrefColsLog): that
-// schedule is taken instead wherever it exists with the same number of passes.
-template <class E>
-struct PrefColsLog {
-  static constexpr unsigned value = E::MIN_COLS_LOG;
-};
-template <>
-struct PrefColsLog<Eng31> {
-  static constexpr unsigned value = Eng31::PREF_COLS_LOG;
-};
+// The schedule of an engine: plan_schedule.hpp's schedule_for at the engine's parameters.  An engine
+// may name a wider column group than MIN_COLS_LOG that it prefers (Eng31::PREF_COLS_LOG).
 template <class E>
 static bool schedule_for(unsigned log_n, unsigned* r, unsigned& p) {
-  if (!schedule(log_n, E::TILE_LOG, E::MIN_COLS_LOG, E::NARROW_FIRST, r, p)) return false;
-  if constexpr (PrefColsLog<E>::value > (unsigned)E::MIN_COLS_LOG) {
-    const char* forced = getenv("NTT_SCHEDULE");
-    unsigned r2[8] = {0}, p2 = 0;
-    if (p >= 2 && !(forced && *forced) &&
-        schedule(log_n, E::TILE_LOG, PrefColsLog<E>::value, E::NARROW_FIRST, r2, p2) && p2 == p)
-      for (unsigned i = 0; i < p; ++i) r[i] = r2[i];
-  }
-  return true;
+  unsigned pref = E::MIN_COLS_LOG;
+  if constexpr (std::is_same_v<E, Eng31>) pref = Eng31::PREF_COLS_LOG;
+  return schedule_for(log_n, E::TILE_LOG, E::MIN_COLS_LOG, pref, E::NARROW_FIRST, r, p);
 }
-
-// NTT_PLAN_IN_PLACE: a palindromic sequence (r_i = r_{p-1-i}, 3 <= r_i <= rmax, schedule_ok) with the
-// fewest passes (>= p0), then the smallest largest radix, then the largest smallest one.  The digit
-// reversal of a palindromic sequence is an involution (k_digitrev_swap).
-static bool schedule_palindrome(unsigned log_n, unsigned tile_log, unsigned rmax, unsigned p0, unsigned* r,
-                                unsigned& p) {
-  if (rmax < 3) return false;
-  const unsigned span = rmax - 2;  // radices 3..rmax
-  for (unsigned pp = (p0 < 2 ? 2 : p0); pp <= 8; ++pp) {
-    const unsigned h = (pp + 1) / 2;
-    unsigned combos = 1;
-    for (unsigned i = 0; i < h; ++i) combos *= span;
-    unsigned best[8] = {0}, bmax = 99, bmin = 0;
-    for (unsigned code = 0; code < combos; ++code) {
-      unsigned v[8], c = code, sum = 0, mx = 0, mn = 99;
-      for (unsigned i = 0; i < h; ++i) {
-        v[i] = 3 + c % span;
-        c /= span;
-      }
-      for (unsigned i = 0; i < pp; ++i) {
-        v[i] = v[i < h ? i : pp - 1 - i];
-        sum += v[i];
-        mx = v[i] > mx ? v[i] : mx;
-        mn = v[i] < mn ? v[i] : mn;
-      }
-      if (sum != log_n || !schedule_ok(v, pp, tile_log)) continue;
-      if (mx < bmax || (mx == bmax && mn > bmin)) {
-        bmax = mx;
-        bmin = mn;
-        for (unsigned i = 0; i < pp; ++i) best[i] = v[i];
-      }
-    }
-    if (bmax != 99) {
-      p = pp;
-      for (unsigned i = 0; i < pp; ++i) r[i] = best[i];
-      return true;
-    }
-  }
-  return false;
-}
-
-// ------------------------------------------------------------------------------ engine encodings
-// The host does all table arithmetic in 32-bit Montgomery form (HostField<NH>), produces canonical
-// values, then encodes them in the engine's own Montgomery domain / limb layout.
-template <class E>
-struct EngHost;
-
-template <int L, int W32, int S, int T>
-struct EngHost<Eng29<L, W32, S, T>> {
-  using E29 = Eng29<L, W32, S, T>;
-  static constexpr int NH = W32;
-  static constexpr int TW = E29::TW;
-  using EA = typename E29::Args;
-  HostField<NH> const* H = nullptr;
-  Vec<NH> kR{};          // B = 2^(29L) mod p, canonical
-  uint32_t pinvB[L] = {};  // p^-1 mod B
-  void init(const HostField<NH>& h) {
-    H = &h;
-    Vec<NH> x{};
-    x[0] = 1;
-    for (int k = 0; k < 29 * L; ++k) x = h.add(x, x);
-    kR = x;
-    uint32_t pw[NH], pl[L];
-    for (int i = 0; i < NH; ++i) pw[i] = h.M.p[i];
-    pack29<L, NH>(pl, pw);
-    inv_mod_B29<L>(pinvB, pl);
-  }
-  static void limbs(const Vec<NH>& c, uint32_t (&x)[L]) {
-    uint32_t w[NH];
-    for (int i = 0; i < NH; ++i) w[i] = c[i];
-    pack29<L, NH>(x, w);
-  }
-  Vec<NH> times_B(const Vec<NH>& c) const { return H->mul(c, H->to_mont(kR)); }  // c B mod p
-  // canonical c -> Shoup table entry (c, floor(c B / p)) as TW words
-  void encode(const Vec<NH>& c, uint32_t* out) const {
-    uint32_t w[L], wr[L], ws[L];
-    limbs(c, w);
-    limbs(times_B(c), wr);
-    shoup_ws29<L>(ws, wr, pinvB);
-    for (int i = 0; i < TW; ++i) out[i] = i < L ? w[i] : (i < 2 * L ? ws[i - L] : 0u);
-  }
-  // entry whose value is c R_e (R_e = B): the left factor of the two-level twiddle products
-  void encode_scaled(const Vec<NH>& c, uint32_t* out) const { encode(times_B(c), out); }
-  bool check_modulus(const uint32_t* p) const {
-    // 2p fits the HBM words (p < 2^(32 W32 - 1)) and 64p <= B = 2^(29L) (lazy bounds up to 33p)
-    int bits = 0;
-    for (int i = NH - 1; i >= 0; --i)
-      if (p[i]) { bits = 32 * i + 32 - __builtin_clz(p[i]); break; }
-    return bits <= 32 * NH - 1 && bits <= 29 * L - 6;
-  }
-  void fill_args(EA& A, const uint32_t* p, const Vec<NH>* w8, const Vec<NH>& ninv) const {
-    eng29_fill_consts<E29, L, NH>(A, p);  // eng29_args.hpp: everything but the twiddles
-    uint32_t tmp[TW];
-    auto to_tw = [&](const Vec<NH>& c, typename E29::Tw& t) {
-      encode(c, tmp);
-      for (int i = 0; i < L; ++i) {
-        t.w[i] = tmp[i];
-        t.ws[i] = tmp[L + i];
-      }
-    };
-    for (int k = 0; k < 3; ++k) to_tw(w8[k], A.w8[k]);
-    to_tw(ninv, A.ninv);
-  }
-};
-
-template <int N, int MEMW_, int SCR_>
-struct EngHost<Eng32<N, MEMW_, SCR_>> {
-  static constexpr int NH = N;
-  using EA = typename Eng32<N, MEMW_, SCR_>::Args;
-  using ET = typename Eng32<N, MEMW_, SCR_>::Tw;
-  HostField<NH> const* H = nullptr;
-  void init(const HostField<NH>& h) { H = &h; }
-  // canonical c -> Shoup pair (c, floor(c 2^32 / p))
-  void encode(const Vec<NH>& c, uint32_t* out) const {
-    out[0] = c[0];
-    out[1] = (uint32_t)(((uint64_t)c[0] << 32) / H->M.p[0]);
-  }
-  // entry whose value is c R_e (R_e = 2^32, the Montgomery radix of Eng32::mulv): c's Montgomery form
-  void encode_scaled(const Vec<NH>& c, uint32_t* out) const { encode(H->to_mont(c), out); }
-  // lazy values up to 4p must fit 32 bits
-  bool check_modulus(const uint32_t* p) const { return p[0] < (1u << 30); }
-  void fill_args(EA& A, const uint32_t* p, const Vec<NH>* w8, const Vec<NH>& ninv) const {
-    A.p = p[0];
-    A.p2 = 2 * p[0];
-    uint32_t inv = 1;
-    for (int i = 0; i < 5; ++i) inv *= 2 - p[0] * inv;  // p^-1 mod 2^32 (Newton)
-    A.pinv = inv;
-    uint32_t t[2];
-    auto tw = [&](const Vec<NH>& c, ET& e) {
-      encode(c, t);
-      e.w[0] = t[0];
-      e.ws = t[1];
-    };
-    for (int k = 0; k < 3; ++k) tw(w8[k], A.w8[k]);
-    tw(ninv, A.ninv);
-  }
-};
-
-// Goldilocks: the host works on the modulus zero-padded to three 32-bit words (the no-carry host
-// Montgomery product needs a top word below 2^31 - 1, and p's own top word is 2^32 - 1); the engine's
-// values and table entries are the canonical low two words, and its radix R_e is 1.
-constexpr uint64_t kGoldilocksP = 0xFFFFFFFF00000001ull;
-template <>
-struct EngHost<Eng64G> {
-  static constexpr int NH = 3;
-  using EA = Eng64G::Args;
-  HostField<NH> const* H = nullptr;
-  void init(const HostField<NH>& h) { H = &h; }
-  void encode(const Vec<NH>& c, uint32_t* out) const {
-    out[0] = c[0];
-    out[1] = c[1];
-  }
-  void encode_scaled(const Vec<NH>& c, uint32_t* out) const { encode(c, out); }
-  bool check_modulus(const uint32_t* p) const {
-    return p[0] == (uint32_t)kGoldilocksP && p[1] == (uint32_t)(kGoldilocksP >> 32) && p[2] == 0u;
-  }
-  void fill_args(EA& A, const uint32_t*, const Vec<NH>* w8, const Vec<NH>& ninv) const {
-    for (int k = 0; k < 3; ++k) encode(w8[k], A.w8[k].w);
-    encode(ninv, A.ninv.w);
-  }
-};
-
-// Eng31: one 32-bit host word; twiddle entries are Shoup pairs, element-format entries w 2^32 mod p (the
-// Montgomery radix of Eng31::mulv), like the P path's, on any odd modulus below 2^31.
-template <>
-struct EngHost<Eng31> {
-  static constexpr int NH = 1;
-  using EA = Eng31::Args;
-  using ET = Eng31::Tw;
-  HostField<NH> const* H = nullptr;
-  void init(const HostField<NH>& h) { H = &h; }
-  void encode(const Vec<NH>& c, uint32_t* out) const {
-    out[0] = c[0];
-    out[1] = f31::shoup_companion(c[0], H->M.p[0]);
-  }
-  void encode_scaled(const Vec<NH>& c, uint32_t* out) const { encode(H->to_mont(c), out); }
-  bool check_modulus(const uint32_t* p) const { return f31::modulus_ok(p[0]); }
-  void fill_args(EA& A, const uint32_t* p, const Vec<NH>* w8, const Vec<NH>& ninv) const {
-    A.p = p[0];
-    A.pinv = f31::pinv32(p[0]);
-    uint32_t t[2];
-    auto tw = [&](const Vec<NH>& c, ET& e) {
-      encode(c, t);
-      e.w[0] = t[0];
-      e.ws = t[1];
-    };
-    for (int k = 0; k < 3; ++k) tw(w8[k], A.w8[k]);
-    tw(ninv, A.ninv);
-  }
-};
 
 template <class E>
 struct PlanImpl final : PlanBase {
@@ -606,20 +184,20 @@ struct PlanImpl final : PlanBase {
   HostField<NH> H;
   EngHost<E> EH;
   typename E::Args Ff{}, Fi{};
-  uint32_t* d_tab = nullptr;
-  uint32_t* d_scratch = nullptr;
+  DevBuf d_tab;
+  DevBuf d_scratch;  // (size_t)n * batch elements of SCRW words, grown on demand (ensure_scratch)
   // per-pass outer twiddle tables (w R_e, HBM element format), one allocation per direction: the
   // forward's at plan creation, the inverse's at the first inverse call (a forward-only user pays for
   // one direction: 2^24 BN254 plan 1.55 -> 1.03 GB)
-  uint32_t* d_fulls[2] = {nullptr, nullptr};
+  DevBuf d_fulls[2];
+  Lazy full_state[2];       // ready: d_fulls[dir] is built; unavailable: the two-level tables serve
   size_t full_off[8] = {};  // element offsets of pass i's table in d_fulls[dir]
   size_t full_elems = 0;    // entries per direction
   bool use_full = false;
-  uint32_t* d_full_sh = nullptr;  // passes >= 2: the same tables as Shoup pairs (E::TW words per entry)
+  DevBuf d_full_sh;               // passes >= 2: the same tables as Shoup pairs (E::TW words per entry)
   size_t full_sh_off[2][8] = {};  // entry offsets into d_full_sh, [dir][pass]
   bool full_sh_ok[8] = {};         // pass i takes its outer twiddles from d_full_sh
   size_t off_pinvB = 0;           // p^-1 mod B (E::W limbs) in d_tab (Shoup-pair table build)
-  size_t scratch_elems = 0;
   // table word offsets
   size_t off_int_f[8] = {0}, off_int_i[8] = {0};
   size_t off_lo_f = 0, off_hi_f = 0, off_lo_i = 0, off_hi_i = 0, off_hi_is = 0, off_r2 = 0;
@@ -627,50 +205,22 @@ struct PlanImpl final : PlanBase {
   size_t off_rm = 0;                    // R_e R^-1 (Montgomery-form pointwise product)
   size_t off_pow2inv = 0;               // 2^-k, k = 0..log_n, E::TW words each (build_fs_table's scale)
   size_t off_hi_ipm = 0;                // inverse hi table scaled by n^-1 R_e (fused polymul, pass 1)
-  uint32_t* d_full_pm = nullptr;        // inverse pass-1 outer twiddles x n^-1 R_e (fused polymul)
-  uint32_t* d_stk_tab = nullptr;        // NTT_PLAN_STOCKHAM: per-pass input-twiddle tables
-  uint32_t* d_naive_pw = nullptr;       // NTT_PLAN_NAIVE: w_n^i R_e, i < n/2 (the reference's `roots`)
-  uint32_t* d_naive_buf = nullptr;      // NTT_PLAN_NAIVE: the bit-reversed copy the rounds work on
-                                        // (NO_SWAP, bealto family: the ping-pong partner of the caller's buffer)
-  size_t off_bealto_pq = 0;             // bealto family: w_{2^max_deg}^j, j < 2^(max_deg - 1), Shoup pairs
-  unsigned bealto_max_deg = 0, bealto_log_g = 0;
-  size_t stk_off[8] = {};               // element offsets into d_stk_tab (pass >= 1)
-  unsigned stk_ord[8] = {};             // Stockham pass i runs radix r[stk_ord[i]] (widest first)
-  uint32_t* d_stk_buf[2] = {nullptr, nullptr};  // NTT_PLAN_STOCKHAM ping-pong buffers (E::MEMW words)
+  DevBuf d_full_pm;                     // inverse pass-1 outer twiddles x n^-1 R_e (fused polymul)
+  Rivals<E, PlanImpl> rivals{*this};    // the rival schedules' state and code (plan_rivals.hpp)
   unsigned lo_bits = 0;
   uint32_t nrand = 1, top_bits = 28;
 
+  // The two-level tables (lo scaled by R_e, hi) that the outer twiddles w_n^e of a direction are computed
+  // from.  The inverse's hi table for pass 1 (index 0) carries n^-1; every other reader takes the plain one.
+  const uint32_t* outer_lo(int dir) const { return d_tab.get() + (dir ? off_los_i : off_los_f); }
+  const uint32_t* outer_hi(int dir, unsigned pass) const {
+    return d_tab.get() + (dir ? (pass == 0 ? off_hi_is : off_hi_i) : off_hi_f);
+  }
+
+  // the members' buffers are freed after this body, with the plan's device current (~PlanBase)
   ~PlanImpl() override {
-    int cur = 0;
-    (void)hipGetDevice(&cur);
+    (void)hipGetDevice(&caller_device);
     (void)hipSetDevice(device);
-    if (d_tab) (void)hipFree(d_tab);
-    if (d_scratch) (void)hipFree(d_scratch);
-    for (auto* p : d_fulls)
-      if (p) (void)hipFree(p);
-    if (d_full_sh) (void)hipFree(d_full_sh);
-    if (d_full_pm) (void)hipFree(d_full_pm);
-    if (d_stk_tab) (void)hipFree(d_stk_tab);
-    if (d_naive_pw) (void)hipFree(d_naive_pw);
-    if (d_naive_buf) (void)hipFree(d_naive_buf);
-    for (auto* p : d_stk_buf)
-      if (p) (void)hipFree(p);
-    if (d_bad) (void)hipFree(d_bad);
-    if (d_coset) (void)hipFree(d_coset);
-    if (d_coset_full) (void)hipFree(d_coset_full);
-    if (d_lde_stage) (void)hipFree(d_lde_stage);
-    if (d_sync) (void)hipFree(d_sync);
-    if (d_sync_ip) (void)hipFree(d_sync_ip);
-    if (d_sync2) (void)hipFree(d_sync2);
-    if (d_trace) (void)hipFree(d_trace);
-    if (d_ipn) (void)hipFree(d_ipn);
-    if (d_pw) (void)hipFree(d_pw);
-    if (d_dbg) (void)hipFree(d_dbg);
-    watch_slot_release(h_watch);
-    for (auto& row : ev)
-      for (auto& e : row)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipSetDevice(cur);
   }
 
   // modulus / generator as NH 32-bit words
@@ -812,14 +362,11 @@ struct PlanImpl final : PlanBase {
         }
       }
     }
-    if ((flags & kBealtoFlags) && !twiddle_only) {
-      // the reference's pq table (GZKP-NTT.cu:489-499, 740-750): max_deg = min(8 - log_g, log_n), one
-      // group per workgroup for bellperson, 2^5 for the improved kernels (GZKP-NTT.cu:1674-1704)
-      if (log_n < 1) return NTT_ERR_ARG;
-      bealto_log_g = (flags & NTT_PLAN_BELLPERSON) ? 0u : 5u;
-      bealto_max_deg = std::min(8u - bealto_log_g, log_n);
-      off_bealto_pq = push_powers(H.pow_u64(w, n >> bealto_max_deg), 1ull << (bealto_max_deg - 1), nullptr);
-    }
+    if (!twiddle_only)
+      if (int rc = rivals.host_tables([&](unsigned shift, uint64_t count) {
+            return push_powers(H.pow_u64(w, n >> shift), count, nullptr);
+          }))
+        return rc;
     {  // pointwise product constants: mulv leaves a b / R_e (R_e the engine's Montgomery radix);
        // multiplying by R_e gives a b, by R_e R^-1 the Montgomery product a b R^-1 (R = 2^(64 limbs64);
        // 2^32 on the 4-byte elements of Eng31)
@@ -862,223 +409,19 @@ struct PlanImpl final : PlanBase {
     (void)hipGetDevice(&cur);
     if (hipSetDevice(device) != hipSuccess) return NTT_ERR_HIP;
     int rc = NTT_OK;
-    if (hipMalloc(&d_tab, host.size() * 4) != hipSuccess ||
-        hipMemcpy(d_tab, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if (!d_tab.alloc(host.size() * 4) ||
+        hipMemcpy(d_tab.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
       rc = NTT_ERR_HIP;
 #if NTT_DEBUG_CHECKS
     // debug builds: the status word every kernel of this plan records check failures in
-    if (rc == NTT_OK && (hipMalloc(&d_dbg, 4) != hipSuccess || hipMemset(d_dbg, 0, 4) != hipSuccess)) rc = NTT_ERR_HIP;
-    Ff.dbg = Fi.dbg = d_dbg;
+    if (rc == NTT_OK && (!d_dbg.alloc(4) || hipMemset(d_dbg.get(), 0, 4) != hipSuccess)) rc = NTT_ERR_HIP;
+    Ff.dbg = Fi.dbg = d_dbg.get();
 #endif
     if (rc == NTT_OK && npass >= 2 && !twiddle_only && !(flags & NTT_PLAN_IN_PLACE)) rc = ensure_scratch(1);
     if (rc == NTT_OK && npass >= 2 && !twiddle_only) rc = build_full_tables();
-    // NTT_PLAN_GZKP runs on the same per-pass tables: Stockham pass i's w_n^((k pi) << (log_n - lgp_i - r_i))
-    // for k < 2^lgp_i is the GZKP DIT pass's w_N^(c d), N = 2^(lgp_i + r_i)
-    if (rc == NTT_OK && (flags & (NTT_PLAN_STOCKHAM | NTT_PLAN_GZKP))) rc = build_stockham();
-    if (rc == NTT_OK && (flags & (NTT_PLAN_NAIVE | NTT_PLAN_NO_SWAP))) rc = build_naive();
-    if (rc == NTT_OK && (flags & kBealtoFlags)) rc = build_bealto();
+    if (rc == NTT_OK) rc = rivals.build();
     (void)hipSetDevice(cur);
     return rc;
-  }
-
-  // NTT_PLAN_STOCKHAM (rival schedule, bellperson family): pass i (i >= 1) multiplies element pi of
-  // group k < p_i = 2^(r_0 + ... + r_{i-1}) by w_n^((k pi) << (log_n - lgp_i - r_i)) from a table in
-  // the column-group-major layout of the pass kernels (k_build_tw with c := k); two ping-pong buffers.
-  int build_stockham() {
-    if constexpr (!HasStockham<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (npass < 2) return NTT_ERR_ARG;
-      // widest radix first: pass i >= 1 needs p_i = 2^(r_0 + ... + r_{i-1}) >= T_i = TILE / R_i
-      for (unsigned i = 0; i < npass; ++i) stk_ord[i] = i;
-      std::stable_sort(stk_ord, stk_ord + npass, [&](unsigned a, unsigned b) { return r[a] > r[b]; });
-      size_t elems = 0;
-      unsigned lgp = 0;
-      const unsigned tl = tile_log_of<E>();
-      for (unsigned i = 0; i < npass; ++i) {
-        const unsigned ri = r[stk_ord[i]];
-        if (i > 0) {
-          if (lgp + ri < tl) return NTT_ERR_ARG;
-          stk_off[i] = elems;
-          elems += 1ull << (lgp + ri);
-        }
-        lgp += ri;
-      }
-      if (hipMalloc(&d_stk_tab, elems * TABW * 4) != hipSuccess) return NTT_ERR_HIP;
-      for (auto*& p : d_stk_buf)
-        if (hipMalloc(&p, (size_t)n * MEMW * 4) != hipSuccess) return NTT_ERR_HIP;
-      lgp = r[stk_ord[0]];
-      for (unsigned i = 1; i < npass; ++i) {
-        const unsigned ri = r[stk_ord[i]];
-        if (launch_build_tw<E>(d_stk_tab + stk_off[i] * TABW, 1ull << (lgp + ri), ri, tl - ri, log_n - lgp - ri,
-                               d_tab + off_los_f, d_tab + off_hi_f, lo_bits, Ff, nullptr) != hipSuccess)
-          return NTT_ERR_HIP;
-        lgp += ri;
-      }
-      return hipDeviceSynchronize() == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-    }
-  }
-
-  // NTT_PLAN_GZKP (rival schedule, GZKP(B, G), GZKP-NTT.cu:115-233): digit reversal into a plan buffer
-  // (`rearrange`; the bit reversal of the reference's radix-2 rounds), contiguous radix-2^r_0 DFTs (the reference's first rounds, `naive` / a GZKP launch
-  // at stride 1), then in-place DIT passes over stride-2^lgp columns with input twiddles; the last
-  // pass writes the caller's buffer.  Widest radix first, as for Stockham (lgp_i >= T_i).
-  int run_gzkp(const uint32_t* in, uint32_t* out, hipStream_t st) {
-    if constexpr (!HasStockham<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      const unsigned tl = tile_log_of<E>();
-      uint32_t* buf = d_stk_buf[0];
-      uint32_t digits[8];
-      for (unsigned i = 0; i < npass; ++i) digits[i] = r[stk_ord[i]];
-      begin(st);
-      hipError_t e = launch_bitrev<E>(in, buf, log_n, digits, npass, st);
-      mark(st);
-      unsigned lgp = 0;
-      for (unsigned i = 0; i < npass && e == hipSuccess; ++i) {
-        const unsigned ri = r[stk_ord[i]];
-        PassArgs<E> A = base_args(false);
-        A.tw_int = d_tab + off_int_f[stk_ord[i]];  // w_R^e for this pass's radix
-        uint32_t* dst = i + 1 == npass ? out : buf;
-        if (i == 0) {  // s = 1: contiguous 2^r_0-point DFTs, batched (grid.y chunks of <= 2^15 blocks)
-          A.batch_stride = ((size_t)1 << ri) * MEMW;
-          const size_t blocks = n >> ri, chunk = size_t(1) << 15;
-          for (size_t b0 = 0; b0 < blocks && e == hipSuccess; b0 += chunk) {
-            const size_t off = (b0 << ri) * MEMW;
-            e = launch_pass<E>(KIND_SINGLE, (int)ri, buf + off, buf + off, A, 1,
-                               (uint32_t)(blocks - b0 < chunk ? blocks - b0 : chunk), st);
-          }
-        } else {
-          A.tw_full = d_stk_tab + stk_off[i] * TABW;  // w_N^(c d), N = 2^(lgp + r_i)
-          A.log_blk = lgp + ri;
-          A.lgp = lgp;
-          A.src_user = 1;
-          e = launch_pass<E>(KIND_DIT, (int)ri, buf, dst, A, (uint32_t)(n >> tl), 1, st);
-        }
-        mark(st);
-        lgp += ri;
-      }
-      return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-    }
-  }
-
-  // NTT_PLAN_NAIVE (rival schedule, the reference's `naive`, GZKP-NTT.cu:59-95 / big-num.cu:67-170):
-  // the bit reversal (`rearrange`), then log2 n radix-2 DIT rounds of one launch each, every round
-  // a full read and write of the vector (HBM-bound; the measure of what the pass kernels' fusion
-  // buys).  The reference's n-entry `roots` table is the n/2 entries its rounds read.
-  int build_naive() {
-    if constexpr (!HasStockham<E>::value) {
-      return NTT_ERR_ARG;  // the rival schedules: P and 4 x 64-bit plans
-    } else {
-      if (log_n < 1 || log_n > 32) return NTT_ERR_ARG;
-      const size_t half = n / 2;
-      if (hipMalloc(&d_naive_pw, half * TABW * 4) != hipSuccess) return NTT_ERR_HIP;
-      if (hipMalloc(&d_naive_buf, (size_t)n * MEMW * 4) != hipSuccess) return NTT_ERR_HIP;
-      if (launch_build_pow<E>(d_naive_pw, half, d_tab + off_los_f, d_tab + off_hi_f, lo_bits, Ff, nullptr) !=
-          hipSuccess)
-        return NTT_ERR_HIP;
-      return hipDeviceSynchronize() == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-    }
-  }
-
-  int run_naive(const uint32_t* in, uint32_t* out, hipStream_t st) {
-    begin(st);
-    hipError_t e = launch_bitrev<E>(in, d_naive_buf, log_n, nullptr, 0, st);  // radix-2 rounds: the bit reversal
-    mark(st);
-    for (unsigned s = 0; s < log_n && e == hipSuccess; ++s)
-      e = launch_naive_round<E>(d_naive_buf, s + 1 == log_n ? out : d_naive_buf, log_n, s, d_naive_pw, Ff, st);
-    mark(st);  // last_launch_ms: [bit reversal, all rounds]
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-  }
-
-  // NTT_PLAN_NO_SWAP (rival schedule, the reference's `naive_no_swap`, GZKP-NTT.cu:237-296): a radix-2
-  // Stockham autosort, one launch per round, ping-pong between the caller's buffer and the plan
-  // buffer (natural order in and out, no bit reversal); an odd round count ends in the plan buffer
-  // and one device copy brings it back.  The same n/2-entry power table as NTT_PLAN_NAIVE.
-  int run_noswap(uint32_t* data, hipStream_t st) {
-    begin(st);
-    hipError_t e = hipSuccess;
-    uint32_t* buf[2] = {data, d_naive_buf};
-    for (unsigned s = 0; s < log_n && e == hipSuccess; ++s)
-      e = launch_noswap_round<E>(buf[s & 1], buf[(s + 1) & 1], log_n, s, d_naive_pw, Ff, st);
-    if (e == hipSuccess && (log_n & 1))
-      e = hipMemcpyAsync(data, d_naive_buf, (size_t)n * MEMW * 4, hipMemcpyDeviceToDevice, st);
-    mark(st);  // last_launch_ms: [all rounds (and the copy)]
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-  }
-
-  // NTT_PLAN_BELLPERSON / NTT_PLAN_IMPROVED_V1..V4 (rival schedules, the reference's bealto.com group
-  // FFT and its four refinements, GZKP-NTT.cu:391-464, 556-1296): rounds of 2^deg-point groups,
-  // deg = min(max_deg, log_n - lgp), one launch each (k_bealto), ping-pong between the caller's buffer
-  // and the plan buffer; an odd round count ends in the plan buffer and one device copy brings it back.
-  int build_bealto() {
-    if constexpr (!HasStockham<E>::value) {
-      return NTT_ERR_ARG;  // the rival schedules: P and 4 x 64-bit plans
-    } else {
-      if (log_n < 1 || log_n > 32 || bealto_max_deg < 1) return NTT_ERR_ARG;
-      if (hipMalloc(&d_naive_buf, (size_t)n * MEMW * 4) != hipSuccess) return NTT_ERR_HIP;
-      return NTT_OK;
-    }
-  }
-  int bealto_variant() const {
-    if (flags & NTT_PLAN_BELLPERSON) return BEALTO_BELLPERSON;
-    if (flags & NTT_PLAN_IMPROVED_V1) return BEALTO_V1;
-    if (flags & NTT_PLAN_IMPROVED_V2) return BEALTO_V2;
-    if (flags & NTT_PLAN_IMPROVED_V3) return BEALTO_V3;
-    return BEALTO_V4;
-  }
-  int run_bealto(uint32_t* data, hipStream_t st) {
-    if constexpr (!HasStockham<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      const int variant = bealto_variant();
-      PassArgs<E> A = base_args(false);
-      A.tw_int = d_tab + off_bealto_pq;
-      A.tw_lo = d_tab + off_los_f;  // lo R_e: (lo R_e) hi, then the Montgomery product leaves x w
-      A.tw_hi = d_tab + off_hi_f;
-      BealtoArgs B{log_n, 0u, 0u, 0u, bealto_max_deg};
-      uint32_t* buf[2] = {data, d_naive_buf};
-      const unsigned nr = (log_n + bealto_max_deg - 1) / bealto_max_deg;
-      const bool per_round = nr + 2 < kEv;  // one profiling interval per round while they fit
-      const char* lab = variant == BEALTO_BELLPERSON ? "g" : "v";
-      begin(st);
-      hipError_t e = hipSuccess;
-      unsigned rounds = 0;
-      while (B.lgp < log_n && e == hipSuccess) {
-        B.deg = std::min(bealto_max_deg, log_n - B.lgp);
-        B.log_g = std::min(bealto_log_g, log_n - B.deg);
-        e = launch_bealto<E>(variant, buf[rounds & 1], buf[(rounds + 1) & 1], A, B, st);
-        if (per_round) mark(st, lab, B.deg);
-        B.lgp += B.deg;
-        ++rounds;
-      }
-      if (e == hipSuccess && (rounds & 1))
-        e = hipMemcpyAsync(data, d_naive_buf, (size_t)n * MEMW * 4, hipMemcpyDeviceToDevice, st);
-      if (!per_round || (rounds & 1)) mark(st, per_round ? "cp" : lab);
-      return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-    }
-  }
-
-  int run_stockham(const uint32_t* in, uint32_t* out, hipStream_t st) {
-    const uint32_t grid = (uint32_t)(n >> tile_log_of<E>());
-    hipError_t e = hipSuccess;
-    unsigned lgp = 0;
-    begin(st);
-    for (unsigned i = 0; i < npass && e == hipSuccess; ++i) {
-      const unsigned ri = r[stk_ord[i]];
-      PassArgs<E> A = base_args(false);
-      A.tw_int = d_tab + off_int_f[stk_ord[i]];  // w_R^e for this pass's radix
-      A.tw_full = i ? d_stk_tab + stk_off[i] * TABW : nullptr;
-      A.log_blk = log_n;
-      A.lgp = lgp;
-      A.src_user = 1;
-      const uint32_t* src = i == 0 ? in : d_stk_buf[(i - 1) & 1];
-      uint32_t* dst = i + 1 == npass ? out : d_stk_buf[i & 1];
-      e = launch_pass<E>(KIND_STOCKHAM, (int)ri, src, dst, A, grid, 1, st);
-      mark(st);
-      lgp += ri;
-    }
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
   }
 
   // Full per-pass outer-twiddle tables: pass i needs N_i entries (N_1 = n, N_2 = n / R_1, ...),
@@ -1107,36 +450,29 @@ struct PlanImpl final : PlanBase {
   // The forward's are built at plan creation, the inverse's at the first inverse call (a forward-only
   // plan never holds them): that build is enqueued on the call's stream ahead of its passes, with no
   // device-wide synchronisation.  If the allocation fails then, the direction keeps its two-level
-  // tables (one more product per element in pass 1) instead of failing the call.
-  bool full_failed[2] = {false, false};
+  // tables (one more product per element in pass 1) instead of failing the call; at
+  // creation (direction 0) the plan reports it.
   int ensure_full(int dir, hipStream_t st) {
-    if (d_fulls[dir] || full_failed[dir]) return NTT_OK;
-    if (hipMalloc(&d_fulls[dir], full_elems * TABW * 4) != hipSuccess) {
-      d_fulls[dir] = nullptr;
-      (void)hipGetLastError();  // clear the sticky allocation error
-      if (dir == 0) return NTT_ERR_HIP;  // at creation: the plan reports it
-      full_failed[dir] = true;
-      return NTT_OK;
-    }
+    const bool ok = full_state[dir].ready([&] { return build_full(dir, st); });
+    return (ok || dir != 0) ? NTT_OK : NTT_ERR_HIP;
+  }
+  bool build_full(int dir, hipStream_t st) {
+    DevBuf& tab = d_fulls[dir];
+    if (!tab.alloc(full_elems * TABW * 4)) return false;
     unsigned blk = log_n;
     for (unsigned i = 0; i + 1 < npass; ++i) {
-      const uint32_t* lo = d_tab + (dir ? off_los_i : off_los_f);
-      const uint32_t* hi = d_tab + (dir ? (i == 0 ? off_hi_is : off_hi_i) : off_hi_f);
       // column-group-major layout of the pass kernel's tiles (T = TILE / R columns per workgroup)
-      if (launch_build_tw<E>(d_fulls[dir] + full_off[i] * TABW, 1ull << blk, r[i], tile_log_of<E>() - r[i], log_n - blk,
-                             lo, hi, lo_bits, dir ? Fi : Ff, st) != hipSuccess) {
+      if (launch_build_tw<E>(tab.get() + full_off[i] * TABW, 1ull << blk, r[i], tile_log_of<E>() - r[i], log_n - blk,
+                             outer_lo(dir), outer_hi(dir, i), lo_bits, dir ? Fi : Ff, st) != hipSuccess) {
         // a partly built table must never be read as a built one: drop it; the
         // direction falls back to the two-level tables (the inverse) or the plan fails (creation)
-        (void)hipFree(d_fulls[dir]);
-        d_fulls[dir] = nullptr;
+        tab.reset();
         (void)hipGetLastError();
-        if (dir == 0) return NTT_ERR_HIP;
-        full_failed[dir] = true;
-        return NTT_OK;
+        return false;
       }
       blk -= r[i];
     }
-    return NTT_OK;
+    return true;
   }
 
   // Column passes whose table is small enough to stay in L2 (N_i entries of E::TW words <= 8 MiB):
@@ -1146,24 +482,16 @@ struct PlanImpl final : PlanBase {
   // Round 5: pass 1 too when its table fits (plans of <= 2^16 points: the four-step's 2^16-point
   // column transforms of 2^24, C4's 2^14-point rows and columns), on engines whose scratch and caller
   // layouts agree (one kernel instance reads both); the inverse's pass-1 table carries n^-1 as its
-  // Montgomery twin does.  NTT_SHOUP_OUTER=0 in the environment keeps the Montgomery tables (A/B
-  // switch); =1 keeps pass 1 on its Montgomery table (round-4 behaviour).
-  static int shoup_outer_env() {
-    static const int v = [] {
-      const char* e = getenv("NTT_SHOUP_OUTER");
-      return e && *e ? atoi(e) : 2;
-    }();
-    return v;
-  }
+  // Montgomery twin does (knob::shoup_outer: 0 none, 1 not pass 1).
   int build_shoup_tables() {
     if constexpr (!E::SHOUP_OUTER) {
       return NTT_OK;
     } else {
-      if (shoup_outer_env() == 0) return NTT_OK;
+      if (knob::shoup_outer() == 0) return NTT_OK;
       if (npass < 2 || !Ff.red_ok) return NTT_OK;  // the Shoup-pair column kernels are FAST instances
       constexpr size_t kMaxTableBytes = 8ull << 20;
       constexpr bool pass1_ok = E::SCRW == E::MEMW;  // pass 1 reads the caller's layout
-      const unsigned i0 = (pass1_ok && shoup_outer_env() >= 2) ? 0u : 1u;
+      const unsigned i0 = (pass1_ok && knob::shoup_outer() >= 2) ? 0u : 1u;
       size_t elems = 0;
       unsigned blk = log_n;
       for (unsigned i = 0; i + 1 < npass; ++i) {
@@ -1179,7 +507,7 @@ struct PlanImpl final : PlanBase {
         for (auto& ok : full_sh_ok) ok = false;
         return NTT_OK;
       }
-      if (hipMalloc(&d_full_sh, 2 * elems * TW * 4) != hipSuccess) return NTT_ERR_HIP;
+      if (!d_full_sh.alloc(2 * elems * TW * 4)) return NTT_ERR_HIP;
       for (int dir = 0; dir < 2; ++dir) {
         blk = log_n;
         for (unsigned i = 0; i + 1 < npass; ++i) {
@@ -1188,11 +516,9 @@ struct PlanImpl final : PlanBase {
             blk -= r[i];
             continue;
           }
-          const uint32_t* lo = d_tab + (dir ? off_los_i : off_los_f);
-          const uint32_t* hi = d_tab + (dir ? (i == 0 ? off_hi_is : off_hi_i) : off_hi_f);
-          if (launch_build_tw_sh<E>(d_full_sh + full_sh_off[dir][i] * TW, 1ull << blk, r[i], tile_log_of<E>() - r[i],
-                                    log_n - blk, lo, hi, lo_bits, dir ? Fi : Ff, d_tab + off_pinvB,
-                                    nullptr) != hipSuccess)
+          if (launch_build_tw_sh<E>(d_full_sh.get() + full_sh_off[dir][i] * TW, 1ull << blk, r[i], tile_log_of<E>() - r[i],
+                                    log_n - blk, outer_lo(dir), outer_hi(dir, i), lo_bits, dir ? Fi : Ff,
+                                    d_tab.get() + off_pinvB, nullptr) != hipSuccess)
             return NTT_ERR_HIP;
           blk -= r[i];
         }
@@ -1222,27 +548,24 @@ struct PlanImpl final : PlanBase {
 
   // ---- coset (low-degree extension): data[j] *= c^j before the forward, c^-j after the inverse
   std::vector<uint32_t> coset_key;  // shift c (NH words) of the cached tables
-  uint32_t* d_coset = nullptr;
-  uint32_t* d_coset_full = nullptr;  // fused coset forward: pass-1 outer twiddles x c^col (n entries)
+  DevBuf d_coset;
+  DevBuf d_coset_full;  // fused coset forward: pass-1 outer twiddles x c^col (n entries)
   bool coset_full_ok = false;
   size_t coset_off[2][3] = {};  // [dir][lo_s, hi, u^d (forward only)] word offsets into d_coset
-  uint32_t* d_lde_stage = nullptr;  // ntt_lde_batch: scaled inputs of the engines without the product at load
-  size_t lde_stage_elems = 0;
+  DevBuf d_lde_stage;  // ntt_lde_batch: scaled inputs of the engines without the product at load
   std::vector<uint32_t> pm2_;    // p - 2 (inversion exponent)
 
-  unsigned long long* d_bad = nullptr;  // canonical-range check counter
+  DevBuf d_bad;  // canonical-range check counter
   int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) override {
     if (!d || !bad) return NTT_ERR_ARG;
-    if (!d_bad && hipMalloc(&d_bad, sizeof(*d_bad)) != hipSuccess) {
-      d_bad = nullptr;
-      return NTT_ERR_HIP;
-    }
+    if (!d_bad && !d_bad.alloc(sizeof(unsigned long long))) return NTT_ERR_HIP;
+    auto* cnt = d_bad.get<unsigned long long>();
     ModWords<MEMW> pw{};
     for (int i = 0; i < NH && i < MEMW; ++i) pw.w[i] = H.M.p[i];
     unsigned long long h = 0;
-    if (hipMemsetAsync(d_bad, 0, sizeof(*d_bad), st) != hipSuccess ||
-        launch_count_noncanonical<E>(static_cast<const uint32_t*>(d), count, pw, d_bad, st) != hipSuccess ||
-        hipMemcpyAsync(&h, d_bad, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipMemsetAsync(cnt, 0, sizeof(h), st) != hipSuccess ||
+        launch_count_noncanonical<E>(static_cast<const uint32_t*>(d), count, pw, cnt, st) != hipSuccess ||
+        hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
       return NTT_ERR_HIP;
     *bad = h;
@@ -1262,8 +585,7 @@ struct PlanImpl final : PlanBase {
     if (!vec_lt<NH>(c, pv) || c == Vec<NH>{}) return NTT_ERR_ARG;
     const std::vector<uint32_t> key(c.begin(), c.end());
     if (key != coset_key) {
-      if (d_coset) (void)hipFree(d_coset);
-      d_coset = nullptr;
+      d_coset.reset();
       coset_key.clear();
       std::vector<uint32_t> host;
       const Vec<NH> cm = H.to_mont(c);
@@ -1277,8 +599,8 @@ struct PlanImpl final : PlanBase {
       // fused forward: u^d, u = c^s (s = n / R_1 columns of pass 1), d < R_1, Shoup entries
       if (npass >= 2) coset_off[0][2] = push_powers_to(host, H.pow_u64(cm, n >> r[0]), 1ull << r[0], nullptr, false);
       coset_full_ok = false;
-      if (hipMalloc(&d_coset, host.size() * 4) != hipSuccess) return NTT_ERR_HIP;
-      if (hipMemcpy(d_coset, host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTT_ERR_HIP;
+      if (!d_coset.alloc(host.size() * 4)) return NTT_ERR_HIP;
+      if (hipMemcpy(d_coset.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTT_ERR_HIP;
       coset_key = key;
     }
     return NTT_OK;
@@ -1289,16 +611,14 @@ struct PlanImpl final : PlanBase {
     if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
     const int dir = inverse ? 1 : 0;
     auto scale = [&]() {
-      return launch_scale_pow<E>(static_cast<uint32_t*>(d), log_n, 1, d_coset + coset_off[dir][0],
-                                 d_coset + coset_off[dir][1], lo_bits, Ff, st) == hipSuccess
-                 ? NTT_OK
-                 : NTT_ERR_HIP;
+      return rc_of(launch_scale_pow<E>(static_cast<uint32_t*>(d), log_n, 1, d_coset.get() + coset_off[dir][0],
+                                       d_coset.get() + coset_off[dir][1], lo_bits, Ff, st));
     };
     if (!inverse) {
       if (coset_fusable()) {  // the scale rides in pass 1: u^d at load, c^col in the outer twiddles
         if (int rc = ensure_coset_full()) return rc;
         uint32_t* x = static_cast<uint32_t*>(d);
-        return run_io(x, nullptr, x, 1, false, st, d_coset_full, d_coset + coset_off[0][2]);
+        return run_io(x, nullptr, x, 1, false, st, d_coset_full.get(), d_coset.get() + coset_off[0][2]);
       }
       if (int rc = scale()) return rc;
       return run(d, 1, false, st);
@@ -1334,24 +654,22 @@ struct PlanImpl final : PlanBase {
         if (hipMemcpyAsync(dst, src, (size_t)batch * eb, hipMemcpyDeviceToDevice, st) != hipSuccess) return NTT_ERR_HIP;
         return NTT_OK;
       }
-      bool fast = false;
-      if constexpr (E::FASTRED) fast = Ff.red_ok != 0;
-      const bool fuse = coset_fusable();
+      const bool fastred = fast(Ff), fuse = coset_fusable();
       const int kind = npass == 1 ? KIND_SINGLE : KIND_COLUMN;
-      if (npass == 0 || !lde_pass_available<E>(kind, (int)r[0], fast) || (fast && npass >= 2 && !fuse))
+      if (npass == 0 || !lde_pass_available<E>(kind, (int)r[0], fastred) || (fastred && npass >= 2 && !fuse))
         return lde_staged(src, dst, n_in, shift != nullptr, batch, st);
       LdeIO L;
       L.n_in = n_in;
       if (fuse) {
         if (!shift && !d_fulls[0]) return lde_staged(src, dst, n_in, false, batch, st);
         if (!shift)  // the plan's own pass-1 table (element format), no product at load
-          return run_io(src, nullptr, dst, batch, false, st, d_fulls[0] + full_off[0] * TABW, nullptr, nullptr, &L);
+          return run_io(src, nullptr, dst, batch, false, st, d_fulls[0].get() + full_off[0] * TABW, nullptr, nullptr, &L);
         if (int rc = ensure_coset_full()) return rc;
-        return run_io(src, nullptr, dst, batch, false, st, d_coset_full, d_coset + coset_off[0][2], nullptr, &L);
+        return run_io(src, nullptr, dst, batch, false, st, d_coset_full.get(), d_coset.get() + coset_off[0][2], nullptr, &L);
       }
       if (shift) {
-        const uint32_t* lo = d_coset + coset_off[0][0];
-        const uint32_t* hi = d_coset + coset_off[0][1];
+        const uint32_t* lo = d_coset.get() + coset_off[0][0];
+        const uint32_t* hi = d_coset.get() + coset_off[0][1];
         const bool at_load = npass == 1 ? lde_mul_at_load<E, KIND_SINGLE>() : lde_mul_at_load<E, KIND_COLUMN>();
         if (at_load) {
           L.lo = lo;
@@ -1359,17 +677,10 @@ struct PlanImpl final : PlanBase {
         } else {
           // the multi-limb engines' first pass has no room for the two table entries: one launch over
           // the batch n_in inputs scales them into the plan's staging buffer, which the pass then reads
-          const size_t need = (size_t)batch * n_in;
-          if (need > lde_stage_elems) {
-            if (d_lde_stage) (void)hipFree(d_lde_stage);
-            d_lde_stage = nullptr;
-            lde_stage_elems = 0;
-            if (hipMalloc(&d_lde_stage, need * eb) != hipSuccess) return NTT_ERR_HIP;
-            lde_stage_elems = need;
-          }
+          if (!d_lde_stage.grow((size_t)batch * n_in * eb)) return NTT_ERR_HIP;
           L.scale_lo = lo;
           L.scale_hi = hi;
-          L.stage = d_lde_stage;
+          L.stage = d_lde_stage.get();
         }
       }
       return run_io(src, nullptr, dst, batch, false, st, nullptr, nullptr, nullptr, &L);
@@ -1384,29 +695,25 @@ struct PlanImpl final : PlanBase {
     if (hipMemsetAsync(dst, 0, (size_t)batch * (size_t)n * eb, st) != hipSuccess ||
         hipMemcpy2DAsync(dst, (size_t)n * eb, src, n_in * eb, n_in * eb, batch, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return NTT_ERR_HIP;
-    if (shifted && launch_scale_pow<E>(dst, log_n, batch, d_coset + coset_off[0][0], d_coset + coset_off[0][1], lo_bits,
+    if (shifted && launch_scale_pow<E>(dst, log_n, batch, d_coset.get() + coset_off[0][0], d_coset.get() + coset_off[0][1], lo_bits,
                                        Ff, st) != hipSuccess)
       return NTT_ERR_HIP;
     return run_io(dst, nullptr, dst, batch, false, st);
   }
 
-  bool coset_fusable() const {
-    if constexpr (!E::FASTRED) {
-      return false;
-    } else {
-      return use_full && npass >= 2 && Ff.red_ok;
-    }
+  // the engine's fast (quotient-estimate) reduction holds for this modulus in direction F
+  static bool fast(const typename E::Args& F) {
+    if constexpr (E::FASTRED) return F.red_ok != 0;
+    else return false;
   }
+  bool coset_fusable() const { return use_full && npass >= 2 && fast(Ff); }
   // Pass-1 outer-twiddle table of the fused coset forward for the cached shift c: entry (col, k) =
   // w_n^(col k) c^col R_e, layout of d_full (built on the device once per shift).
   int ensure_coset_full() {
     if (coset_full_ok) return NTT_OK;
-    if (!d_coset_full && hipMalloc(&d_coset_full, (size_t)n * TABW * 4) != hipSuccess) {
-      d_coset_full = nullptr;
-      return NTT_ERR_HIP;
-    }
-    if (launch_build_tw<E>(d_coset_full, n, r[0], tile_log_of<E>() - r[0], 0, d_tab + off_los_f, d_tab + off_hi_f,
-                           lo_bits, Ff, nullptr, d_coset + coset_off[0][0], d_coset + coset_off[0][1]) != hipSuccess ||
+    if (!d_coset_full && !d_coset_full.alloc((size_t)n * TABW * 4)) return NTT_ERR_HIP;
+    if (launch_build_tw<E>(d_coset_full.get(), n, r[0], tile_log_of<E>() - r[0], 0, outer_lo(0), outer_hi(0, 0), lo_bits,
+                           Ff, nullptr, d_coset.get() + coset_off[0][0], d_coset.get() + coset_off[0][1]) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess)
       return NTT_ERR_HIP;
     coset_full_ok = true;
@@ -1426,16 +733,7 @@ struct PlanImpl final : PlanBase {
     }
   }
 
-  int ensure_scratch(unsigned batch) {
-    const size_t need = (size_t)n * batch;
-    if (need <= scratch_elems) return NTT_OK;
-    if (d_scratch) (void)hipFree(d_scratch);
-    d_scratch = nullptr;
-    scratch_elems = 0;
-    if (hipMalloc(&d_scratch, need * SCRW * 4) != hipSuccess) return NTT_ERR_HIP;
-    scratch_elems = need;
-    return NTT_OK;
-  }
+  int ensure_scratch(unsigned batch) { return d_scratch.grow((size_t)n * batch * SCRW * 4) ? NTT_OK : NTT_ERR_HIP; }
 
   // debug builds: element extents of a pass's src / dst from the transform's first element (n per
   // transform, n 2^il in Mode I); the four-step maps into the caller's exchange blocks stay unchecked
@@ -1444,6 +742,16 @@ struct PlanImpl final : PlanBase {
     A.dbg_src_n = (io && (A.fs & FS_MAP_IN)) ? ~(size_t)0 : ext;
     A.dbg_dst_n = (io && (A.fs & FS_MAP_OUT)) ? ~(size_t)0 : ext;
   }
+  // a four-step piece's position maps (`bits`: which of FS_MAP_IN / FS_MAP_OUT this pass takes)
+  void set_fs(PassArgs<E>& A, const FsIO* io, uint32_t il, uint32_t bits) const {
+    if (!io) return;
+    A.fs = io->fs & (bits | FS_IL | FS_MAP_EPI);
+    A.il = il;
+    A.min = io->min;
+    A.mout = io->mout;
+    A.mepi = io->mepi;
+  }
+  static int rc_of(hipError_t e) { return e == hipSuccess ? NTT_OK : NTT_ERR_HIP; }
   PassArgs<E> base_args(bool inverse) const {
     PassArgs<E> A;
     memset(&A, 0, sizeof(A));
@@ -1470,17 +778,135 @@ struct PlanImpl final : PlanBase {
 
   int run(void* d, unsigned batch, bool inverse, hipStream_t st) override {
     if (!d || batch == 0 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
-    if ((flags & NTT_PLAN_STOCKHAM) && !inverse && batch == 1 && d_stk_tab)
-      return run_stockham(static_cast<uint32_t*>(d), static_cast<uint32_t*>(d), st);
-    if ((flags & NTT_PLAN_GZKP) && !inverse && batch == 1 && d_stk_tab)
-      return run_gzkp(static_cast<uint32_t*>(d), static_cast<uint32_t*>(d), st);
-    if ((flags & NTT_PLAN_NAIVE) && !inverse && batch == 1 && d_naive_pw)
-      return run_naive(static_cast<uint32_t*>(d), static_cast<uint32_t*>(d), st);
-    if ((flags & NTT_PLAN_NO_SWAP) && !inverse && batch == 1 && d_naive_pw)
-      return run_noswap(static_cast<uint32_t*>(d), st);
-    if ((flags & kBealtoFlags) && !inverse && batch == 1 && d_naive_buf)
-      return run_bealto(static_cast<uint32_t*>(d), st);
+    if (int rc = NTT_OK; !inverse && batch == 1 && rivals.run(static_cast<uint32_t*>(d), st, rc)) return rc;
     return run_io(static_cast<uint32_t*>(d), nullptr, static_cast<uint32_t*>(d), batch, inverse, st);
+  }
+
+  // The arguments of a multi-pass transform's launches: column passes 0..npass-2, then the final pass
+  // (PA[npass - 1]).  The parameters are run_io's.
+  void pass_args(PassArgs<E>* PA, bool inverse, bool inplace, uint32_t il, const uint32_t* in2, const uint32_t* full0,
+                 const uint32_t* tw_in, const FsIO* io, const LdeIO* lde) const {
+    const int dir = inverse ? 1 : 0;
+    const size_t* off_int = inverse ? off_int_i : off_int_f;
+    const bool full_dir = use_full && d_fulls[dir];  // else: the two-level tables
+    unsigned blk = log_n;
+    for (unsigned i = 0; i + 1 < npass; ++i) {
+      PassArgs<E>& A = PA[i];
+      A = base_args(inverse);
+      A.tw_int = d_tab.get() + off_int[i];
+      A.tw_lo = outer_lo(dir);
+      A.tw_hi = outer_hi(dir, i);
+      // pass 1 of a memory-bound engine (8-B P path) computes its outer twiddles from the
+      // L2-resident two-level tables: two 32-bit products are cheaper than streaming an n-entry table (A/B: knob)
+      A.tw_full = (full_dir && (i > 0 || E::PASS1_FULL_TABLE || knob::pass1_full()))
+                      ? d_fulls[dir].get() + full_off[i] * TABW
+                      : nullptr;
+      if (d_full_sh && full_sh_ok[i] && (i > 0 || full_dir)) {
+        A.tw_full = d_full_sh.get() + full_sh_off[dir][i] * TW;
+        A.tw_sh = 1;
+      }
+      if (i == 0 && in2) {  // the fused prologues bring their own pass-1 tables (w R_e)
+        A.src2 = in2;
+        A.tw_full = d_full_pm.get();
+        A.tw_sh = 0;
+      }
+      if (i == 0 && tw_in) {
+        A.tw_in = tw_in;
+        A.tw_full = full0;
+        A.tw_sh = 0;
+      }
+      if (i == 0 && lde) {  // PRO_LDE: short inputs; without the fused table, two-level outer twiddles
+        A.src_stride = lde->n_in * MEMW;
+        if (full0) {  // the shift's cached table with tw_in, or the plan's own pass-1 table without
+          A.tw_full = full0;
+          A.tw_sh = 0;
+        } else {
+          A.tw_full = nullptr;
+          A.tw_sh = 0;
+          A.tw_in = lde->lo;
+          A.tw_in_hi = lde->hi;
+        }
+      }
+      A.log_blk = blk + il;
+      A.log_m = log_n - blk;
+      A.src_user = (i == 0) ? 1u : 0u;
+      set_fs(A, io, il, i == 0 ? FS_MAP_IN : 0u);
+      blk -= r[i];
+    }
+    PassArgs<E>& A = PA[npass - 1];
+    A = base_args(inverse);
+    A.tw_int = d_tab.get() + off_int[npass - 1];
+    A.r1 = r[0];
+    A.nmid = npass - 2;
+    // middle digits k_2..k_{p-1}, least significant (k_{p-1}) first
+    for (unsigned m = 0; m < A.nmid; ++m) {
+      const unsigned idx = npass - 2 - m;  // pass index (0-based) of digit k_{idx+1}
+      A.mid_bits[m] = r[idx];
+      unsigned off = 0;
+      for (unsigned j = 1; j < idx; ++j) off += r[j];
+      A.mid_off[m] = off;
+    }
+    set_fs(A, io, il, FS_MAP_OUT);
+    if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
+    if (inplace) A.flags |= 2u;
+    for (unsigned i = 0; i < npass; ++i) set_extents(PA[i], io, il);
+    if (lde) PA[0].dbg_src_n = lde->n_in;
+    // XCD-grouped tile order (k_pass flag bit 2) for the column passes after the first whose runs are
+    // shorter than a 128-B line (the 8-B path's 4-B scratch at radix 512: 64-B runs), so that the
+    // two tiles sharing each line meet on one XCD's L2.  Passes of one column per tile (radix 4096 on
+    // the 4096-element tiles) read and write 32-B runs, their final pass's stores too: every such
+    // pass takes the order, so the four tiles of each 128-B line run together.  knob::xcd_order: 0 off,
+    // 1 on every column pass, 3 not on the one-column passes (A/B).
+    const int xcd_order = knob::xcd_order();
+    if (!io && xcd_order > 0)
+      for (unsigned i = 0; i < npass; ++i) {
+        const unsigned cols = 1u << (tile_log_of<E>() - r[i]);
+        const unsigned run_bytes = cols * SCRW * 4;
+        const bool column = i + 1 < npass;
+        if ((column && (xcd_order == 1 || (i > 0 && run_bytes < 128))) || (cols == 1 && xcd_order != 3))
+          PA[i].flags |= 4u;
+      }
+  }
+
+  // The whole batch-1 transform as ONE launch, where the plan has such a schedule (NTT_PLAN_SINGLE_LAUNCH;
+  // built on first use) and these passes fit it: true when it was launched, rc its status.  Two passes
+  // on the 4096-element tiles (k_fused2b, in place k_fused2bi), else three on Eng256 (k_fused3 / k_fused3b,
+  // in place k_fused3bi).
+  bool single_launch(const PassArgs<E>* PA, const uint32_t* in, uint32_t* work, uint32_t* out, bool inplace,
+                     hipStream_t st, int& rc) {
+    constexpr bool two = fused2_engine<E>();
+    if constexpr (!two && !std::is_same_v<E, Eng256>) {
+      return false;
+    } else {
+      if (!(two ? npass == 2 && fused2_ready(PA, inplace) : inplace ? fused_ip_ready(PA) : fused_ready(PA)))
+        return false;
+      FusedArgs F = two ? (inplace ? fargs2_ip : fargs2) : (inplace ? fargs_ip : fargs);
+      F.wd = watchdog(F.wd.abort);
+      if (two) F.trace = fused_trace_buffer(F.nwg);
+      PassArgs<E> A1 = PA[0], B = PA[npass - 1];
+      if (inplace) {  // every pass in the caller's buffer, no scratch
+        A1.ipn_go = F.sync + F.rbase;  // pass 1's stores wait for the residency decision (barrier 1)
+        A1.wd = F.wd;
+        B.flags &= ~2u;
+        B.ipn_sync = F.sync;
+        B.ipn_go = F.sync + F.rbase + (two ? 64 : 96);  // the final pass's barrier (the third / fourth): its go word
+        B.ipn_shards = F.shards;                        // its arrival shards (cumulative, like the top counter)
+        B.wd = F.wd;
+        in = out;
+        work = nullptr;
+      }
+      hipError_t e;
+      {
+        FusedSerial order(device, st);
+        if constexpr (two) e = launch_fused2<E>((int)r[0], (int)r[1], in, work, out, A1, B, F, st);
+        else e = launch_fused3<E>((int)r[0], (int)r[1], (int)r[2], in, work, out, A1, PA[1], B, F, st);
+        order.done(e);
+      }
+      mark(st, "b");
+      if (F.trace && e == hipSuccess) dump_fused_trace(F, inplace, st);
+      rc = e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+      return true;
+    }
   }
 
   // One transform (or a batch): reads `in` (and, for a fused polymul inverse, `in2`: the first pass
@@ -1491,14 +917,6 @@ struct PlanImpl final : PlanBase {
              const uint32_t* full0 = nullptr, const uint32_t* tw_in = nullptr, const FsIO* io = nullptr,
              const LdeIO* lde = nullptr) {
     const uint32_t il = (io && (io->fs & FS_IL)) ? io->il : 0u;
-    auto set_fs = [&](PassArgs<E>& A, uint32_t bits) {
-      if (!io) return;
-      A.fs = io->fs & (bits | FS_IL | FS_MAP_EPI);
-      A.il = il;
-      A.min = io->min;
-      A.mout = io->mout;
-      A.mepi = io->mepi;
-    };
     if (io && (log_n == 0 || npass == 0)) return NTT_ERR_ARG;  // four-step pieces are >= 8 points
     if (log_n == 0) {
       if (out != in && hipMemcpyAsync(out, in, (size_t)batch * MEMW * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -1519,15 +937,15 @@ struct PlanImpl final : PlanBase {
     }
     if (npass == 0) {
       PassArgs<E> A = base_args(inverse);
-      A.tw_int = d_tab + off_int[0];
+      A.tw_int = d_tab.get() + off_int[0];
       A.flags = inverse ? 1u : 0u;
       e = launch_naive<E>(in, out, A, batch, st);
       mark(st, "n");
     } else if (npass == 1) {
       PassArgs<E> A = base_args(inverse);
-      A.tw_int = d_tab + off_int[0];
+      A.tw_int = d_tab.get() + off_int[0];
       A.flags = (inverse && !(io && io->no_scale)) ? 1u : 0u;  // no_scale: n^-1 folded in by the caller
-      set_fs(A, FS_MAP_IN | FS_MAP_OUT);
+      set_fs(A, io, il, FS_MAP_IN | FS_MAP_OUT);
       if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
       set_extents(A, io, il);
       if (lde) {  // low-degree extension of at most one tile: one transform per workgroup
@@ -1545,18 +963,14 @@ struct PlanImpl final : PlanBase {
       }
       const uint32_t nt = il ? (1u << il) : batch;  // transforms of this launch
       // KIND_ROWS: TILE / n transforms per workgroup (the final pass's block layout: wave-uniform trivial
-      // twiddles, 4-wave workgroups) when the engine has it and the count divides; NTT_ROWS=0: one per
+      // twiddles, 4-wave workgroups) when the engine has it and the count divides; knob::rows off: one per
       // workgroup (KIND_SINGLE)
       const unsigned rows_log = (unsigned)tile_log_of<E>() - r[0];
-      static const bool rows_env = [] {
-        const char* v = getenv("NTT_ROWS");
-        return !(v && *v == '0');
-      }();
       bool rows = false;
       if constexpr (HasRows<E>::value) {
         bool fast_ok = true;  // the quotient-estimate engines run KIND_ROWS in their FAST form only
         if constexpr (E::FASTRED) fast_ok = Ff.red_ok != 0;
-        rows = rows_env && fast_ok && r[0] >= (unsigned)kRowsMinLog && r[0] <= (unsigned)rows_max_log<E>() &&
+        rows = knob::rows() && fast_ok && r[0] >= (unsigned)kRowsMinLog && r[0] <= (unsigned)rows_max_log<E>() &&
                rows_log >= 1 && nt >= (1u << rows_log) && (nt & ((1u << rows_log) - 1)) == 0;
       }
       if (rows) {
@@ -1574,165 +988,18 @@ struct PlanImpl final : PlanBase {
       // NTT_PLAN_IN_PLACE (not for four-step pieces, whose passes map positions): every pass reads and
       // writes `out`'s positions, the final pass included; the digit reversal follows as tile swaps
       const bool inplace = (flags & NTT_PLAN_IN_PLACE) && !io;
-      uint32_t* work = inplace ? out : d_scratch;
-      if (!inplace) {
+      if (!inplace)
         if (int rc = ensure_scratch(il ? (1u << il) : batch)) return rc;
-        work = d_scratch;
-      }
+      uint32_t* work = inplace ? out : d_scratch.get();
       const uint32_t grid = (uint32_t)((n << il) >> tile_log_of<E>());
       if (use_full)
         if (int rc = ensure_full(inverse ? 1 : 0, st)) return rc;
-      const bool full_dir = use_full && d_fulls[inverse ? 1 : 0];  // else: the two-level tables
-      // the passes' arguments: column passes 0..npass-2, then the final pass
+      // build the arguments, try the single launch, else launch the passes
       PassArgs<E> PA[8];
-      unsigned blk = log_n;
-      for (unsigned i = 0; i + 1 < npass; ++i) {
-        PassArgs<E>& A = PA[i];
-        A = base_args(inverse);
-        A.tw_int = d_tab + off_int[i];
-        A.tw_lo = d_tab + (inverse ? off_los_i : off_los_f);
-        A.tw_hi = d_tab + (inverse ? (i == 0 ? off_hi_is : off_hi_i) : off_hi_f);
-        // pass 1 of a memory-bound engine (8-B P path) computes its outer twiddles from the
-        // L2-resident two-level tables: two 32-bit products are cheaper than streaming an n-entry table
-        static const bool p1_full = [] {  // NTT_PASS1_FULL=1: pass 1 streams its table on every engine (A/B)
-          const char* v = getenv("NTT_PASS1_FULL");
-          return v && atoi(v) > 0;
-        }();
-        A.tw_full = (full_dir && (i > 0 || E::PASS1_FULL_TABLE || p1_full)) ? d_fulls[inverse ? 1 : 0] + full_off[i] * TABW
-                                                                             : nullptr;
-        if (d_full_sh && full_sh_ok[i] && (i > 0 || full_dir)) {
-          A.tw_full = d_full_sh + full_sh_off[inverse ? 1 : 0][i] * TW;
-          A.tw_sh = 1;
-        }
-        if (i == 0 && in2) {  // the fused prologues bring their own pass-1 tables (w R_e)
-          A.src2 = in2;
-          A.tw_full = d_full_pm;
-          A.tw_sh = 0;
-        }
-        if (i == 0 && tw_in) {
-          A.tw_in = tw_in;
-          A.tw_full = full0;
-          A.tw_sh = 0;
-        }
-        if (i == 0 && lde) {  // PRO_LDE: short inputs; without the fused table, two-level outer twiddles
-          A.src_stride = lde->n_in * MEMW;
-          if (full0) {  // the shift's cached table with tw_in, or the plan's own pass-1 table without
-            A.tw_full = full0;
-            A.tw_sh = 0;
-          } else {
-            A.tw_full = nullptr;
-            A.tw_sh = 0;
-            A.tw_in = lde->lo;
-            A.tw_in_hi = lde->hi;
-          }
-        }
-        A.log_blk = blk + il;
-        A.log_m = log_n - blk;
-        A.src_user = (i == 0) ? 1u : 0u;
-        set_fs(A, i == 0 ? FS_MAP_IN : 0u);
-        blk -= r[i];
-      }
-      PassArgs<E>& A = PA[npass - 1];
-      A = base_args(inverse);
-      A.tw_int = d_tab + off_int[npass - 1];
-      A.r1 = r[0];
-      A.nmid = npass - 2;
-      // middle digits k_2..k_{p-1}, least significant (k_{p-1}) first
-      for (unsigned m = 0; m < A.nmid; ++m) {
-        const unsigned idx = npass - 2 - m;  // pass index (0-based) of digit k_{idx+1}
-        A.mid_bits[m] = r[idx];
-        unsigned off = 0;
-        for (unsigned j = 1; j < idx; ++j) off += r[j];
-        A.mid_off[m] = off;
-      }
-      set_fs(A, FS_MAP_OUT);
-      if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
-      if (inplace) A.flags |= 2u;
-      for (unsigned i = 0; i < npass; ++i) set_extents(PA[i], io, il);
-      if (lde) PA[0].dbg_src_n = lde->n_in;
-      // XCD-grouped tile order (k_pass flag bit 2) for the column passes after the first whose runs are
-      // shorter than a 128-B line (the 8-B path's 4-B scratch at radix 512: 64-B runs), so that the
-      // two tiles sharing each line meet on one XCD's L2.  Passes of one column per tile (radix 4096 on
-      // the 4096-element tiles) read and write 32-B runs, their final pass's stores too: every such
-      // pass takes the order, so the four tiles of each 128-B line run together.  NTT_XCD_ORDER=0 off,
-      // =1 on every column pass, =3 not on the one-column passes (A/B).
-      static const int xcd_order = [] {
-        const char* v = getenv("NTT_XCD_ORDER");
-        return v && *v ? atoi(v) : 2;
-      }();
-      if (!io && xcd_order > 0)
-        for (unsigned i = 0; i < npass; ++i) {
-          const unsigned cols = 1u << (tile_log_of<E>() - r[i]);
-          const unsigned run_bytes = cols * SCRW * 4;
-          const bool column = i + 1 < npass;
-          if ((column && (xcd_order == 1 || (i > 0 && run_bytes < 128))) || (cols == 1 && xcd_order != 3))
-            PA[i].flags |= 4u;
-        }
-      if constexpr (fused2_engine<E>()) {  // 2^20 on 4096-element tiles: the two-pass single launch
-        if (!io && !lde && batch == 1 && npass == 2 && fused_enabled() && fused2_ready(PA, inplace)) {
-          FusedArgs F = inplace ? fargs2_ip : fargs2;
-          F.wd = watchdog(F.wd.abort);
-          F.trace = fused_trace_buffer(F.nwg);
-          {
-            FusedSerial order(device, st);
-            if (inplace) {  // k_fused2bi: residency (barrier 1), pass barrier 2, the final pass's barrier 3
-              PassArgs<E> A1 = PA[0];
-              A1.ipn_go = F.sync + F.rbase;  // pass 1's stores wait for the residency decision
-              A1.wd = F.wd;
-              PassArgs<E> B = A;
-              B.flags &= ~2u;
-              B.ipn_sync = F.sync;
-              B.ipn_go = F.sync + F.rbase + 64;
-              B.ipn_shards = F.shards;
-              B.wd = F.wd;
-              e = launch_fused2<E>((int)r[0], (int)r[1], out, nullptr, out, A1, B, F, st);
-            } else {
-              e = launch_fused2<E>((int)r[0], (int)r[1], in, work, out, PA[0], A, F, st);
-            }
-            order.done(e);
-          }
-          mark(st, "b");
-          if (F.trace && e == hipSuccess) dump_fused_trace(F, inplace, st);
-          return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-        }
-      }
-      if constexpr (std::is_same_v<E, Eng256>) {  // the engine k_fused3 is instantiated for
-        if (!io && !lde && !inplace && batch == 1 && fused_enabled() && fused_ready(PA)) {
-          // one persistent launch for the three passes (NTT_PLAN_SINGLE_LAUNCH, k_fused3)
-          FusedArgs F = fused_args();
-          F.wd = watchdog(F.wd.abort);
-          {
-            FusedSerial order(device, st);
-            e = launch_fused3<E>((int)r[0], (int)r[1], (int)r[2], in, work, out, PA[0], PA[1], PA[2], F, st);
-            order.done(e);
-          }
-          mark(st, "b");
-          return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-        }
-      }
-      if constexpr (std::is_same_v<E, Eng256>) {
-        if (!io && inplace && batch == 1 && fused_enabled() && fused_ip_ready(PA)) {
-          // the in-place single launch (k_fused3bi): three passes in the caller's buffer, no scratch
-          FusedArgs F = fargs_ip;
-          F.wd = watchdog(F.wd.abort);
-          PassArgs<E> A1 = PA[0];
-          A1.ipn_go = F.sync + F.rbase;  // pass 1's stores wait for the residency decision (barrier 1)
-          A1.wd = F.wd;
-          PassArgs<E> B = A;
-          B.flags &= ~2u;
-          B.ipn_sync = F.sync;
-          B.ipn_go = F.sync + F.rbase + 96;  // the fourth barrier's go word
-          B.ipn_shards = F.shards;           // its arrival shards (cumulative, like the top counter)
-          B.wd = F.wd;
-          {
-            FusedSerial order(device, st);
-            e = launch_fused3<E>((int)r[0], (int)r[1], (int)r[2], out, nullptr, out, A1, PA[1], B, F, st);
-            order.done(e);
-          }
-          mark(st, "b");
-          return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-        }
-      }
+      pass_args(PA, inverse, inplace, il, in2, full0, tw_in, io, lde);
+      const PassArgs<E>& A = PA[npass - 1];
+      if (!io && !lde && batch == 1 && fused_enabled())
+        if (int rc = NTT_OK; single_launch(PA, in, work, out, inplace, st, rc)) return rc;
       for (unsigned i = 0; i + 1 < npass && e == hipSuccess; ++i) {
         const uint32_t* src = (i == 0) ? in : work;
         if (i == 0 && lde) {
@@ -1747,10 +1014,10 @@ struct PlanImpl final : PlanBase {
         // the final pass writes natural positions in place, the digit reversal fused (k_final_ipn)
         PassArgs<E> B = A;
         B.flags &= ~2u;
-        B.ipn_sync = d_ipn;
-        B.ipn_order = d_ipn + 32 * (2 + ipn_slabs);
+        B.ipn_sync = d_ipn.get();
+        B.ipn_order = d_ipn.get() + 32 * (2 + ipn_slabs);
         B.ipn_strips = ipn_strips;
-        B.wd = watchdog(d_ipn + 32 * (1 + ipn_slabs));
+        B.wd = watchdog(d_ipn.get() + 32 * (1 + ipn_slabs));
         e = launch_final_ipn<E>((int)r[npass - 1], out, B, grid, st);
         mark(st, "i", r[npass - 1]);
       } else if (e == hipSuccess) {
@@ -1764,11 +1031,7 @@ struct PlanImpl final : PlanBase {
           D.nmid = A.nmid;
           for (unsigned m = 0; m < A.nmid; ++m) D.mid_bits[m] = A.mid_bits[m], D.mid_off[m] = A.mid_off[m];
           D.batch_stride = (size_t)n * MEMW;
-          static const int drev_diag = [] {
-            const char* v = getenv("NTT_DREV_DIAG");
-            return v ? atoi(v) : 1;
-          }();
-          D.diag = drev_diag ? 1u : 0u;
+          D.diag = knob::drev_diag() ? 1u : 0u;
           e = launch_digitrev_swap<E>(out, D, batch, st);
           mark(st, "d");
         }
@@ -1777,140 +1040,131 @@ struct PlanImpl final : PlanBase {
     return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
   }
 
-  // ---- fused single-launch schedule (NTT_PLAN_SINGLE_LAUNCH, k_fused3 in ntt_kernels_impl.hpp)
-  uint32_t* d_sync = nullptr;  // FusedArgs::sync words (zeroed at creation; each launch leaves them zeroed)
-  FusedArgs fargs{};
-  bool fused_built = false, fused_ok = false;
-  // NTT_SINGLE_LAUNCH=1 / =0 in the environment forces the schedule on / off for every plan (A/B)
+  // ---- the single-launch schedules (NTT_PLAN_SINGLE_LAUNCH) and the in-place final pass: state built
+  // on the plan's first use of it (Lazy), each with its own geometry of sync words
+  // knob::single_launch forces the schedule on / off for every plan (A/B); unset: the plan's flag
   bool fused_enabled() const {
-    static const int env = [] {
-      const char* v = getenv("NTT_SINGLE_LAUNCH");
-      return v && *v ? atoi(v) : -1;
-    }();
+    const int env = knob::single_launch();
     return env >= 0 ? env > 0 : (flags & NTT_PLAN_SINGLE_LAUNCH) != 0;
   }
-  // 3-pass FAST 256-bit plans whose passes 1 and 2 take full tables (pass 2: Shoup pairs), and whose
-  // radices the fused kernel is instantiated for; built on first use
+  // The sync words of a schedule with inter-workgroup waits (its builder has taken the plan's watchdog
+  // slot, alloc_watch, before its capacity query): `words` zeroed words in `buf`, followed by `tail` when
+  // given (each launch leaves the words zeroed).  Synchronous.
+  bool alloc_sync(DevBuf& buf, size_t words, const std::vector<uint32_t>* tail = nullptr) {
+    const size_t extra = tail ? tail->size() : 0;
+    if (!buf.alloc((words + extra) * 4) || hipMemset(buf.get(), 0, words * 4) != hipSuccess) return false;
+    if (extra && hipMemcpy(buf.get() + words, tail->data(), extra * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return false;
+    return hipDeviceSynchronize() == hipSuccess;
+  }
+  static void fused_verbose(const char* form, uint32_t tiles, uint32_t nwg, uint32_t cap, uint32_t mode = 0) {
+    if (knob::fused_verbose())
+      fprintf(stderr, form, mode), fprintf(stderr, ", %u tiles per pass, %u workgroups (capacity %u)\n", tiles, nwg, cap);
+  }
+  // what both 3-pass single launches need of the passes: full tables for passes 1 and 2 (pass 2: Shoup
+  // pairs), no fused prologue
+  static bool fused3_passes_ok(const PassArgs<E>* PA) {
+    return PA[0].tw_full && PA[1].tw_full && PA[1].tw_sh && !PA[0].src2 && !PA[0].tw_in;
+  }
+
+  // ---- k_fused3 (ntt_kernels_impl.hpp): 3-pass FAST 256-bit plans whose passes 1 and 2 take full tables
+  // and whose radices the fused kernel is instantiated for
+  DevBuf d_sync;  // FusedArgs::sync words
+  FusedArgs fargs{};
+  Lazy fused_state;
   bool fused_ready(const PassArgs<E>* PA) {
-    if (!fused_built) {
-      fused_built = true;
-      fused_ok = build_fused();
-    }
-    return fused_ok && PA[0].tw_full && PA[1].tw_full && PA[1].tw_sh && !PA[0].src2 && !PA[0].tw_in;
+    return fused_state.ready([&] { return build_fused(); }) && fused3_passes_ok(PA);
   }
   bool build_fused() {
     if constexpr (!std::is_same_v<E, Eng256>) {
       return false;
     } else {
-    if (npass != 3 || !use_full || !d_full_sh || !full_sh_ok[1] || !Ff.red_ok) return false;
-    if (!alloc_watch()) return false;
-    const unsigned tl = tile_log_of<E>();
-    // NTT_FUSED_MODE=0: the dataflow form (per-tile hand-offs), =1: the grid-barrier form (default);
-    // read when the plan builds its fused schedule (its first single-launch call)
-    const char* mv = getenv("NTT_FUSED_MODE");
-    const uint32_t mode = (mv && *mv == '0') ? 0u : 1u;
-    uint32_t cap = 0;
-    if (fused3_capacity<E>((int)r[0], (int)r[1], (int)r[2], device, &cap, mode) != hipSuccess || cap == 0) return false;
-    const unsigned r1 = r[0], r2 = r[1], r3 = r[2];
-    const unsigned lt1 = tl - r1, lt2 = tl - r2, lt3 = tl - r3, lu = lt1 > lt2 ? lt1 : lt2;
-    if (r3 < lu || r1 < lt3) return false;  // schedule_ok guarantees both; kept as the kernel's contract
-    FusedArgs F{};
-    F.tiles = (uint32_t)(n >> tl);
-    F.nwg = F.tiles < cap ? F.tiles : cap;
-    F.k1_mask = (1u << (r3 - lt1)) - 1;
-    F.k1_shift = lu - lt1;
-    F.cg_log = r3 - lt2;
-    F.k2_shift = lu - lt2;
-    F.t3_log = lt3;
-    F.r2 = r2;
-    F.n12 = 1u << (r3 - lu);
-    F.n23 = 1u << (r1 - lt3);
-    F.need12 = 1u << (lu - lt1 + r2);
-    F.need23 = 1u << r2;
-    F.mode = mode;
-    if (getenv("NTT_FUSED_VERBOSE"))
-      fprintf(stderr, "libntt: fused schedule mode %u, %u tiles per pass, %u workgroups (capacity %u)\n", mode, F.tiles,
-              F.nwg, cap);
-    if (const char* v = getenv("NTT_FUSED_DBG")) F.dbg = (uint32_t)atoi(v);
-    F.rbase = (4 + F.n12 + F.n23 + 31) & ~31u;
-    const size_t words = F.rbase + 32 * (F.n12 + F.n23);  // then the abort word on a line of its own
-    // then the abort word and the 8 barrier shards, each on a line of its own
-    if (hipMalloc(&d_sync, (words + 32 * 9) * 4) != hipSuccess) {
-      d_sync = nullptr;
-      return false;
-    }
-    if (hipMemset(d_sync, 0, (words + 32 * 9) * 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return false;
-    F.sync = d_sync;
-    F.wd.abort = d_sync + words;
-    F.shards = d_sync + words + 32;
-    fargs = F;
-    return true;
+      if (npass != 3 || !use_full || !d_full_sh || !full_sh_ok[1] || !Ff.red_ok || !alloc_watch()) return false;
+      const unsigned tl = tile_log_of<E>();
+      const uint32_t mode = knob::fused_mode();  // 0: the dataflow form (per-tile hand-offs), 1: grid barriers
+      uint32_t cap = 0;
+      if (fused3_capacity<E>((int)r[0], (int)r[1], (int)r[2], device, &cap, mode) != hipSuccess || cap == 0) return false;
+      const unsigned r1 = r[0], r2 = r[1], r3 = r[2];
+      const unsigned lt1 = tl - r1, lt2 = tl - r2, lt3 = tl - r3, lu = lt1 > lt2 ? lt1 : lt2;
+      if (r3 < lu || r1 < lt3) return false;  // schedule_ok guarantees both; kept as the kernel's contract
+      FusedArgs F{};
+      F.tiles = (uint32_t)(n >> tl);
+      F.nwg = F.tiles < cap ? F.tiles : cap;
+      F.k1_mask = (1u << (r3 - lt1)) - 1;
+      F.k1_shift = lu - lt1;
+      F.cg_log = r3 - lt2;
+      F.k2_shift = lu - lt2;
+      F.t3_log = lt3;
+      F.r2 = r2;
+      F.n12 = 1u << (r3 - lu);
+      F.n23 = 1u << (r1 - lt3);
+      F.need12 = 1u << (lu - lt1 + r2);
+      F.need23 = 1u << r2;
+      F.mode = mode;
+      fused_verbose("libntt: fused schedule mode %u", F.tiles, F.nwg, cap, mode);
+      F.dbg = knob::fused_dbg();
+      F.rbase = (4 + F.n12 + F.n23 + 31) & ~31u;
+      const size_t words = F.rbase + 32 * (F.n12 + F.n23);
+      // then the abort word and the 8 barrier shards, each on a line of its own
+      if (!alloc_sync(d_sync, words + 32 * 9)) return false;
+      F.sync = d_sync.get();
+      F.wd.abort = F.sync + words;
+      F.shards = F.sync + words + 32;
+      fargs = F;
+      return true;
     }
   }
-  const FusedArgs& fused_args() const { return fargs; }
 
-  // ---- the two-pass single launch on 4096-element tiles (NTT_PLAN_SINGLE_LAUNCH, 2^20 4-limb plans:
-  // k_fused2b, and k_fused2bi in place; ntt_kernels_impl.hpp).  Plain launches of at most the occupancy
-  // query's workgroups; the in-place form needs every one of the 256 final tiles resident.
+  // ---- the two-pass single launch on 4096-element tiles (2^20 4-limb plans: k_fused2b, and k_fused2bi
+  // in place; ntt_kernels_impl.hpp).  Plain launches of at most the occupancy query's workgroups; the
+  // in-place form needs every one of the 256 final tiles resident.
   // Sync words: [0] top arrivals, [1] exits; go words at 32, 64, 96 (in place: residency, pass barrier,
   // final barrier); abort at 128; shards at 160 + 32 s.
-  uint32_t* d_sync2 = nullptr;
+  DevBuf d_sync2;
   FusedArgs fargs2{}, fargs2_ip{};
-  int fused2_state[2] = {0, 0};  // [in place]: 0 not built, 1 ready, -1 unavailable
+  Lazy fused2_state[2];  // [in place]
+  bool fused2_built(bool inplace) {
+    return fused2_state[inplace ? 1 : 0].ready([&] { return build_fused2(inplace); });
+  }
   bool fused2_ready(const PassArgs<E>* PA, bool inplace) {
-    int& st = fused2_state[inplace ? 1 : 0];
-    if (st == 0) st = build_fused2(inplace) ? 1 : -1;
-    return st > 0 && PA[0].tw_full && !PA[0].tw_sh && !PA[0].src2 && !PA[0].tw_in;
+    return fused2_built(inplace) && PA[0].tw_full && !PA[0].tw_sh && !PA[0].src2 && !PA[0].tw_in;
   }
   bool build_fused2(bool inplace) {
     if constexpr (!fused2_engine<E>()) {
       return false;
     } else {
-      if (npass != 2 || r[0] != 10 || r[1] != 10 || !use_full || !Ff.red_ok) return false;
-      if (!alloc_watch()) return false;
+      if (npass != 2 || r[0] != 10 || r[1] != 10 || !use_full || !Ff.red_ok || !alloc_watch()) return false;
       const uint32_t tiles = (uint32_t)(n >> tile_log_of<E>()), mode = inplace ? 4u : 3u;
       uint32_t cap = 0;
       if (fused2_capacity<E>((int)r[0], (int)r[1], device, &cap, mode) != hipSuccess || cap == 0) return false;
       if (inplace && cap < tiles) return false;
-      if (!d_sync2) {
-        if (hipMalloc(&d_sync2, 416 * 4) != hipSuccess) {
-          d_sync2 = nullptr;
-          (void)hipGetLastError();
-          return false;
-        }
-        if (hipMemset(d_sync2, 0, 416 * 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return false;
-      }
+      if (!d_sync2 && !alloc_sync(d_sync2, 416)) return false;
       FusedArgs F{};
       F.tiles = tiles;
       F.nwg = inplace ? tiles : (tiles < cap ? tiles : cap);
       F.mode = mode;
       F.rbase = 32;
-      F.sync = d_sync2;
-      F.wd.abort = d_sync2 + 128;
-      F.shards = d_sync2 + 160;
-      if (getenv("NTT_FUSED_VERBOSE"))
-        fprintf(stderr, "libntt: two-pass single launch (mode %u), %u tiles per pass, %u workgroups (capacity %u)\n",
-                mode, tiles, F.nwg, cap);
+      F.sync = d_sync2.get();
+      F.wd.abort = F.sync + 128;
+      F.shards = F.sync + 160;
+      fused_verbose("libntt: two-pass single launch (mode %u)", tiles, F.nwg, cap, mode);
       (inplace ? fargs2_ip : fargs2) = F;
       return true;
     }
   }
-  // NTT_FUSED_TRACE (diagnostics): the stamps buffer, and its dump after the call
-  unsigned long long* d_trace = nullptr;
+  // knob::fused_trace_path (diagnostics): the stamps buffer, and its dump after the call
+  DevBuf d_trace;
   unsigned long long* fused_trace_buffer(uint32_t nwg) {
-    if (!fused_trace_path()) return nullptr;
-    if (!d_trace && hipMalloc(&d_trace, (size_t)4 * 8 * 1024) != hipSuccess) {
-      d_trace = nullptr;
-      (void)hipGetLastError();
-    }
-    return (d_trace && nwg <= 1024) ? d_trace : nullptr;
+    if (!knob::fused_trace_path()) return nullptr;
+    if (!d_trace) (void)d_trace.alloc((size_t)4 * 8 * 1024);
+    return (d_trace && nwg <= 1024) ? d_trace.get<unsigned long long>() : nullptr;
   }
   void dump_fused_trace(const FusedArgs& F, bool inplace, hipStream_t st) {
     std::vector<unsigned long long> h((size_t)4 * F.nwg);
     if (hipStreamSynchronize(st) != hipSuccess ||
         hipMemcpy(h.data(), F.trace, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
       return;
-    if (FILE* f = fopen(fused_trace_path(), "a")) {
+    if (FILE* f = fopen(knob::fused_trace_path(), "a")) {
       fprintf(f, "{\"kernel\": \"%s\", \"log_n\": %u, \"nwg\": %u, \"stamps\": [", inplace ? "k_fused2bi" : "k_fused2b",
               log_n, F.nwg);
       for (size_t i = 0; i < h.size(); ++i) fprintf(f, "%s%llu", i ? ", " : "", h[i]);
@@ -1919,28 +1173,18 @@ struct PlanImpl final : PlanBase {
     }
   }
   bool single_launch_ready() override {
-    if constexpr (!fused2_engine<E>()) {
-      return false;
-    } else {
-      const bool inplace = (flags & NTT_PLAN_IN_PLACE) != 0;
-      if (ensure_full(0, nullptr) != NTT_OK || !d_fulls[0]) return false;
-      int& st = fused2_state[inplace ? 1 : 0];
-      if (st == 0) st = build_fused2(inplace) ? 1 : -1;
-      return st > 0;
-    }
+    if constexpr (fused2_engine<E>())
+      return ensure_full(0, nullptr) == NTT_OK && d_fulls[0] && fused2_built((flags & NTT_PLAN_IN_PLACE) != 0);
+    return false;
   }
 
   // ---- the in-place single launch (NTT_PLAN_SINGLE_LAUNCH on an NTT_PLAN_IN_PLACE plan, k_fused3bi):
   // 3-pass palindromic FAST 256-bit schedules whose tiles all fit the device at once (2^18 .. 2^20)
-  uint32_t* d_sync_ip = nullptr;  // [0] top arrivals, [1] exits; go words at 32 (residency), 64, 96, 128; abort at 160; shards at 192
+  DevBuf d_sync_ip;  // [0] top arrivals, [1] exits; go words at 32 (residency), 64, 96, 128; abort at 160; shards at 192 + 32 s
   FusedArgs fargs_ip{};
-  bool fused_ip_built = false, fused_ip_ok = false;
+  Lazy fused_ip_state;
   bool fused_ip_ready(const PassArgs<E>* PA) {
-    if (!fused_ip_built) {
-      fused_ip_built = true;
-      fused_ip_ok = build_fused_ip();
-    }
-    return fused_ip_ok && PA[0].tw_full && PA[1].tw_full && PA[1].tw_sh && !PA[0].src2 && !PA[0].tw_in;
+    return fused_ip_state.ready([&] { return build_fused_ip(); }) && fused3_passes_ok(PA);
   }
   bool build_fused_ip() {
     if constexpr (!std::is_same_v<E, Eng256>) {
@@ -1955,18 +1199,11 @@ struct PlanImpl final : PlanBase {
       F.tiles = F.nwg = tiles;
       F.mode = 2;
       F.rbase = 32;
-      if (const char* v = getenv("NTT_FUSED_VERBOSE"))
-        fprintf(stderr, "libntt: in-place single launch, %u tiles per pass, %u workgroups (capacity %u)\n", tiles,
-                tiles, cap);
-      // go words at 32 (residency), 64, 96, 128; abort at 160; barrier shards at 192 + 32 s
-      if (hipMalloc(&d_sync_ip, 448 * 4) != hipSuccess) {
-        d_sync_ip = nullptr;
-        return false;
-      }
-      if (hipMemset(d_sync_ip, 0, 448 * 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return false;
-      F.sync = d_sync_ip;
-      F.wd.abort = d_sync_ip + 160;
-      F.shards = d_sync_ip + 192;
+      fused_verbose("libntt: in-place single launch", tiles, tiles, cap);
+      if (!alloc_sync(d_sync_ip, 448)) return false;
+      F.sync = d_sync_ip.get();
+      F.wd.abort = F.sync + 160;
+      F.shards = F.sync + 192;
       fargs_ip = F;
       return true;
     }
@@ -1980,31 +1217,25 @@ struct PlanImpl final : PlanBase {
     clear_trip();
     if (d_dbg) {  // debug builds: NTT_DBG_* bits (engines.hpp)
       uint32_t w = 0;
-      if (hipMemcpy(&w, d_dbg, 4, hipMemcpyDeviceToHost) != hipSuccess) return NTT_ERR_HIP;
-      if (w && hipMemset(d_dbg, 0, 4) != hipSuccess) return NTT_ERR_HIP;
+      if (hipMemcpy(&w, d_dbg.get(), 4, hipMemcpyDeviceToHost) != hipSuccess) return NTT_ERR_HIP;
+      if (w && hipMemset(d_dbg.get(), 0, 4) != hipSuccess) return NTT_ERR_HIP;
       *bad |= w;
     }
     return NTT_OK;
   }
-  uint32_t* d_dbg = nullptr;  // debug builds (NTT_DEBUG_CHECKS): the kernels' check-failure bits
+  DevBuf d_dbg;  // debug builds (NTT_DEBUG_CHECKS): the kernels' check-failure bits
 
   // ---- in-place final pass with the fused digit reversal (NTT_PLAN_IN_PLACE, k_final_ipn)
-  uint32_t* d_ipn = nullptr;  // 32 (1 + slabs) sync words, then the slab order table
+  DevBuf d_ipn;  // 32 (2 + slabs) sync words (line 0, one line per slab, the abort line), then the slab order table
   uint32_t ipn_slabs = 0, ipn_strips = 0;
-  bool ipn_built = false, ipn_ok = false;
-  // NTT_IPN=0 in the environment keeps the separate tile-swap pass (A/B)
+  Lazy ipn_state;
+  // knob::ipn off keeps the separate tile-swap pass (A/B)
   bool ipn_ready(const PassArgs<E>& A) {
-    if (!ipn_built) {
-      ipn_built = true;
-      const char* v = getenv("NTT_IPN");
-      ipn_ok = !(v && v[0] == '0') && build_ipn(A);
-    }
-    return ipn_ok;
+    return ipn_state.ready([&] { return knob::ipn() && build_ipn(A); });
   }
   bool build_ipn(const PassArgs<E>& A) {
     const unsigned tl = tile_log_of<E>(), rp = r[npass - 1];
-    if (npass < 2 || r[0] != rp || rp > 9 || tl < rp) return false;
-    if (!alloc_watch()) return false;
+    if (npass < 2 || r[0] != rp || rp > 9 || tl < rp || !alloc_watch()) return false;
     const unsigned mid_log = log_n - r[0] - rp;
     ipn_slabs = 1u << mid_log;
     ipn_strips = 1u << (r[0] - (tl - rp));  // R_1 / T, T = TILE / R_p
@@ -2033,16 +1264,7 @@ struct PlanImpl final : PlanBase {
         seen[q] = 1;
       }
     }
-    const size_t sync_words = 32 * (2 + (size_t)ipn_slabs);  // line 0, one line per slab, the abort line
-    if (hipMalloc(&d_ipn, (sync_words + order.size()) * 4) != hipSuccess) {
-      d_ipn = nullptr;
-      return false;
-    }
-    if (hipMemset(d_ipn, 0, sync_words * 4) != hipSuccess ||
-        hipMemcpy(d_ipn + sync_words, order.data(), order.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess)
-      return false;
-    return true;
+    return alloc_sync(d_ipn, 32 * (2 + (size_t)ipn_slabs), &order);
   }
 
   // ---- distributed four-step pieces (ntt_rplan, ntt_amd/csrc/ntt_rplan.cpp)
@@ -2064,61 +1286,41 @@ struct PlanImpl final : PlanBase {
     }
     // a mapped piece (the column pieces of ntt_rplan_inverse_cols_piece): the product gathered into a
     // plan-owned buffer first (out's other pieces may still be in flight)
-    if (count > pw_elems) {
-      if (d_pw) (void)hipFree(d_pw);
-      d_pw = nullptr;
-      pw_elems = 0;
-      if (hipMalloc(&d_pw, count * MEMW * 4) != hipSuccess) return NTT_ERR_HIP;
-      pw_elems = count;
-    }
+    if (!d_pw.grow(count * MEMW * 4)) return NTT_ERR_HIP;
     const size_t off = (flags & NTT_PLAN_MONTGOMERY_IO) ? off_rm : off_r2;
-    if (launch_pointwise<E>(pin, static_cast<const uint32_t*>(in2), d_pw, count, Ff, d_tab + off, st,
+    if (launch_pointwise<E>(pin, static_cast<const uint32_t*>(in2), d_pw.get(), count, Ff, d_tab.get() + off, st,
                             (io.fs & FS_MAP_IN) ? &io.min : nullptr) != hipSuccess)
       return NTT_ERR_HIP;
     FsIO io2 = io;
     io2.fs &= ~FS_MAP_IN;
-    return run_io(d_pw, nullptr, pout, batch, true, st, nullptr, nullptr, &io2);
+    return run_io(d_pw.get(), nullptr, pout, batch, true, st, nullptr, nullptr, &io2);
   }
-  uint32_t* d_pw = nullptr;  // gathered pointwise products of mapped pieces (run_fs), on first use
-  size_t pw_elems = 0;
+  DevBuf d_pw;  // gathered pointwise products of mapped pieces (run_fs), on first use
 
   // scale_log k > 0: every entry also carries 2^-k (the four-step's row n2^-1, folded into the inverse
   // columns' epilogue so that the single-pass inverse rows need no scaling product)
   int build_fs_table(void* table, unsigned log_rows, unsigned log_cols, uint64_t row0, uint64_t col0, bool inverse,
                      unsigned scale_log, hipStream_t st) override {
     if (!table || log_rows + log_cols > 40 || scale_log > log_n) return NTT_ERR_ARG;
-    const uint32_t* lo = d_tab + (inverse ? off_los_i : off_los_f);
-    const uint32_t* hi = d_tab + (inverse ? off_hi_i : off_hi_f);
-    const uint32_t* scale = scale_log ? d_tab + off_pow2inv + (size_t)scale_log * TW : nullptr;
-    return launch_build_fs_tw<E>(static_cast<uint32_t*>(table), log_rows, log_cols, row0, col0, log_n, lo, hi,
-                                 lo_bits, inverse ? Fi : Ff, st, scale) == hipSuccess
-               ? NTT_OK
-               : NTT_ERR_HIP;
+    const uint32_t *lo = outer_lo(inverse), *hi = outer_hi(inverse, 1);
+    const uint32_t* scale = scale_log ? d_tab.get() + off_pow2inv + (size_t)scale_log * TW : nullptr;
+    return rc_of(launch_build_fs_tw<E>(static_cast<uint32_t*>(table), log_rows, log_cols, row0, col0, log_n, lo, hi,
+                                       lo_bits, inverse ? Fi : Ff, st, scale));
   }
 
   size_t table_entry_bytes() const override { return (size_t)TABW * 4; }
 
   // Fused polymul is available for multi-pass FAST plans with full outer-twiddle tables.
-  bool polymul_fusable() const {
-    if constexpr (!E::FASTRED) {
-      return false;
-    } else {
-      return use_full && npass >= 2 && Fi.red_ok && !(flags & NTT_PLAN_MONTGOMERY_IO);
-    }
-  }
+  bool polymul_fusable() const { return use_full && npass >= 2 && fast(Fi) && !(flags & NTT_PLAN_MONTGOMERY_IO); }
   // Inverse pass-1 outer-twiddle table scaled by n^-1 R_e (built on first use, same layout as d_full).
   // Built on the call's stream ahead of the passes that read it (no device-wide synchronisation).
   int ensure_polymul_table(hipStream_t st) {
     if (d_full_pm) return NTT_OK;
     const size_t elems = 1ull << log_n;
-    if (hipMalloc(&d_full_pm, elems * TABW * 4) != hipSuccess) {
-      d_full_pm = nullptr;
-      return NTT_ERR_HIP;
-    }
-    if (launch_build_tw<E>(d_full_pm, elems, r[0], tile_log_of<E>() - r[0], 0, d_tab + off_los_i,
-                           d_tab + off_hi_ipm, lo_bits, Fi, st) != hipSuccess) {
-      (void)hipFree(d_full_pm);  // never leave a partly built table behind as if it were built
-      d_full_pm = nullptr;
+    if (!d_full_pm.alloc(elems * TABW * 4)) return NTT_ERR_HIP;
+    if (launch_build_tw<E>(d_full_pm.get(), elems, r[0], tile_log_of<E>() - r[0], 0, outer_lo(1),
+                           d_tab.get() + off_hi_ipm, lo_bits, Fi, st) != hipSuccess) {
+      d_full_pm.reset();  // never leave a partly built table behind as if it were built
       return NTT_ERR_HIP;
     }
     return NTT_OK;
@@ -2153,7 +1355,7 @@ struct PlanImpl final : PlanBase {
 
   int pointwise_n(const uint32_t* a, const uint32_t* b, uint32_t* c, size_t count, hipStream_t st) {
     const size_t off = (flags & NTT_PLAN_MONTGOMERY_IO) ? off_rm : off_r2;
-    return launch_pointwise<E>(a, b, c, count, Ff, d_tab + off, st) == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+    return launch_pointwise<E>(a, b, c, count, Ff, d_tab.get() + off, st) == hipSuccess ? NTT_OK : NTT_ERR_HIP;
   }
 
   int pointwise(const void* a, const void* b, void* c, hipStream_t st) override {
@@ -2165,30 +1367,26 @@ struct PlanImpl final : PlanBase {
   int fill(void* d, uint64_t count, int kind, uint64_t seed, uint64_t row0, unsigned log_inner, unsigned log_stride,
            hipStream_t st) override {
     if (!d || (kind != 0 && kind != 1)) return NTT_ERR_ARG;
-    hipError_t e = launch_fill<E>(kind, static_cast<uint32_t*>(d), count, seed, nrand, top_bits, row0, log_inner,
-                                  log_stride, st);
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+    return rc_of(launch_fill<E>(kind, static_cast<uint32_t*>(d), count, seed, nrand, top_bits, row0, log_inner,
+                                  log_stride, st));
   }
 
   int twiddle_pack(const void* src, void* dst, unsigned log_rows, unsigned log_len, unsigned log_bw, uint64_t row0,
                    bool inverse, uint64_t peer_stride, hipStream_t st) override {
     if (!src || !dst || src == dst || log_bw > log_len || log_rows + log_len > 40) return NTT_ERR_ARG;
     if (peer_stride < (1ull << (log_rows + log_bw))) return NTT_ERR_ARG;  // peer chunks must not overlap
-    const uint32_t* lo = d_tab + (inverse ? off_los_i : off_los_f);
-    const uint32_t* hi = d_tab + (inverse ? off_hi_i : off_hi_f);
-    hipError_t e = launch_twiddle_pack<E>(static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), log_rows,
+    const uint32_t *lo = outer_lo(inverse), *hi = outer_hi(inverse, 1);
+    return rc_of(launch_twiddle_pack<E>(static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), log_rows,
                                           log_len, log_bw, row0, log_n, lo, hi, lo_bits, inverse ? Fi : Ff,
-                                          peer_stride, st);
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+                                          peer_stride, st));
   }
 
   int transpose(const void* src, void* dst, unsigned log_rows, unsigned log_cols, unsigned log_blk_rows,
                 uint64_t blk_stride, hipStream_t st) override {
     if (!src || !dst || src == dst || log_rows + log_cols > 40 || log_blk_rows > log_rows) return NTT_ERR_ARG;
     if (blk_stride < (1ull << (log_blk_rows + log_cols))) return NTT_ERR_ARG;
-    hipError_t e = launch_transpose<E>(static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), log_rows,
-                                       log_cols, log_blk_rows, blk_stride, st);
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+    return rc_of(launch_transpose<E>(static_cast<const uint32_t*>(src), static_cast<uint32_t*>(dst), log_rows,
+                                       log_cols, log_blk_rows, blk_stride, st));
   }
 };
 
@@ -2206,11 +1404,30 @@ static const FieldDef kFields[6] = {
     {{0x7f000001ull, 0, 0, 0}, 3},   // KoalaBear, 2^31 - 2^24 + 1
 };
 
+// modulus and generator as 32-bit words, the form PlanImpl::init takes
+static void split_limbs(uint32_t* p32, uint32_t* g32, const uint64_t* p64, const uint64_t* g64, unsigned limbs64) {
+  for (unsigned i = 0; i < limbs64; ++i) {
+    p32[2 * i] = (uint32_t)p64[i];
+    p32[2 * i + 1] = (uint32_t)(p64[i] >> 32);
+    g32[2 * i] = (uint32_t)g64[i];
+    g32[2 * i + 1] = (uint32_t)(g64[i] >> 32);
+  }
+}
+// a plan of engine E into `out`; nothing is kept of one whose creation failed
+template <class E>
+static int make_impl(std::unique_ptr<PlanBase>& out, const uint32_t* p32, const uint32_t* g32, unsigned log_n,
+                     int device, unsigned flags) {
+  auto impl = std::make_unique<PlanImpl<E>>();
+  const int rc = impl->init(p32, g32, log_n, device, flags);
+  if (rc == NTT_OK) out = std::move(impl);
+  return rc;
+}
+
 static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const uint64_t* g64, unsigned limbs64,
                      unsigned log_n, int device, unsigned flags) {
   if (log_n > 40) return NTT_ERR_ARG;
   if (limbs64 != 1 && limbs64 != 4 && limbs64 != 6) return NTT_ERR_ARG;  // before packing into p32[12] / g32[12]
-  const unsigned rivals = flags & (NTT_PLAN_STOCKHAM | NTT_PLAN_GZKP | NTT_PLAN_NAIVE | NTT_PLAN_NO_SWAP | kBealtoFlags);
+  const unsigned rivals = flags & kRivalFlags;
   if (rivals & (rivals - 1)) return NTT_ERR_ARG;  // one rival schedule per plan
   if ((flags & NTT_PLAN_IN_PLACE) && (rivals || (flags & NTT_PLAN_TWIDDLE_ONLY)))
     return NTT_ERR_ARG;
@@ -2227,58 +1444,23 @@ static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const 
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return NTT_ERR_NODEV;
   if (device < 0 || device >= ndev) return NTT_ERR_ARG;
   uint32_t p32[12] = {0}, g32[12] = {0};
-  for (unsigned i = 0; i < limbs64; ++i) {
-    p32[2 * i] = (uint32_t)p64[i];
-    p32[2 * i + 1] = (uint32_t)(p64[i] >> 32);
-    g32[2 * i] = (uint32_t)g64[i];
-    g32[2 * i + 1] = (uint32_t)(g64[i] >> 32);
-  }
-  int rc;
-  if (elem32) {
-    auto impl = std::make_unique<PlanImpl<Eng31>>();
-    rc = impl->init(p32, g32, log_n, device, flags);
-    out = std::move(impl);
-  } else if (goldilocks) {
-    auto impl = std::make_unique<PlanImpl<Eng64G>>();
-    rc = impl->init(p32, g32, log_n, device, flags);
-    out = std::move(impl);
-  } else if (limbs64 == 1) {
+  split_limbs(p32, g32, p64, g64, limbs64);
+  if (elem32) return make_impl<Eng31>(out, p32, g32, log_n, device, flags);
+  if (goldilocks) return make_impl<Eng64G>(out, p32, g32, log_n, device, flags);
+  const bool inplace = (flags & NTT_PLAN_IN_PLACE) != 0;
+  if (limbs64 == 1) {
     if (p64[0] >= (1ull << 31)) return NTT_ERR_FIELD;  // `long long` path: 31-bit primes
-    if (flags & NTT_PLAN_IN_PLACE) {  // in place needs 8-B scratch elements (the caller's layout)
-      auto impl = std::make_unique<PlanImpl<EngPI>>();
-      rc = impl->init(p32, g32, log_n, device, flags);
-      out = std::move(impl);
-    } else {
-      auto impl = std::make_unique<PlanImpl<EngP>>();
-      rc = impl->init(p32, g32, log_n, device, flags);
-      out = std::move(impl);
-    }
-  } else if (limbs64 == 4) {
-    auto impl = std::make_unique<PlanImpl<Eng256>>();
-    rc = impl->init(p32, g32, log_n, device, flags);
-    out = std::move(impl);
-  } else if (limbs64 == 6) {
-    // the 384-bit element layout: 256-bit arithmetic when the modulus allows it (BN254 Fr,
-    // BLS12-381 Fr: the upper two 64-bit limbs of every element are zero), 14 limbs otherwise
-    if (p64[4] == 0 && p64[5] == 0 && (p64[3] >> 63) == 0 && (flags & NTT_PLAN_IN_PLACE)) {
-      // in place: the intermediates live in the caller's 48-B elements (no 32-B plan scratch)
-      auto impl = std::make_unique<PlanImpl<Eng256wI>>();
-      rc = impl->init(p32, g32, log_n, device, flags);
-      out = std::move(impl);
-    } else if (p64[4] == 0 && p64[5] == 0 && (p64[3] >> 63) == 0) {
-      auto impl = std::make_unique<PlanImpl<Eng256w>>();
-      rc = impl->init(p32, g32, log_n, device, flags);
-      out = std::move(impl);
-    } else {
-      auto impl = std::make_unique<PlanImpl<Eng384>>();
-      rc = impl->init(p32, g32, log_n, device, flags);
-      out = std::move(impl);
-    }
-  } else {
-    return NTT_ERR_ARG;
+    // in place needs 8-B scratch elements (the caller's layout)
+    return inplace ? make_impl<EngPI>(out, p32, g32, log_n, device, flags)
+                   : make_impl<EngP>(out, p32, g32, log_n, device, flags);
   }
-  if (rc != NTT_OK) out.reset();
-  return rc;
+  if (limbs64 == 4) return make_impl<Eng256>(out, p32, g32, log_n, device, flags);
+  // the 384-bit element layout: 256-bit arithmetic when the modulus allows it (BN254 Fr, BLS12-381 Fr:
+  // the upper two 64-bit limbs of every element are zero), 14 limbs otherwise.  In place: the
+  // intermediates live in the caller's 48-B elements (no 32-B plan scratch)
+  if (p64[4] != 0 || p64[5] != 0 || (p64[3] >> 63) != 0) return make_impl<Eng384>(out, p32, g32, log_n, device, flags);
+  return inplace ? make_impl<Eng256wI>(out, p32, g32, log_n, device, flags)
+                 : make_impl<Eng256w>(out, p32, g32, log_n, device, flags);
 }
 
 // BASELINE config 2 (2^20, 4 x 64-bit limbs): a single transform runs fastest on 4096-element tiles,
@@ -2286,15 +1468,7 @@ static int make_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const 
 // against 0.114 ms (BN254), 0.102 against 0.108 (BLS12-381), DESIGN §4.  Batched calls keep the
 // 1024-element tiles, which overlap the batch's transforms better (batch 4: 0.082 against 0.091 ms
 // per transform).  So a default 4-limb plan of 2^20 holds a second plan of 4096-element tiles for
-// one vector's transforms (forward, inverse, coset, polymul).  Environment NTT_WIDE_TILES=0: none.
-static bool wide_tiles_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("NTT_WIDE_TILES");
-    return !(v && *v == '0');
-  }();
-  return on;
-}
-
+// one vector's transforms (forward, inverse, coset, polymul); knob::wide_tiles off: none.
 // The second plan is an optimisation: when it cannot be built the plan runs alone, and nothing of the
 // failure may leak into the plan's calls.  A failed hipMalloc inside its init leaves the error as the
 // thread's last HIP error, which the next launch check (hipGetLastError) would return as NTT_ERR_HIP
@@ -2313,48 +1487,30 @@ static bool wide_flags_ok(unsigned flags) {
 }
 // 2^24 (the headline) on the same tiles in two passes, 12 + 12 with one column per column-pass tile:
 // one HBM round trip of the vector fewer than 8 + 8 + 8 on the 1024-element tiles.
-// NTT_TWO_PASS_24=1 routes a default 2^24 4-limb plan's single-vector transforms there.
-static bool two_pass_24_enabled() {
-  static const bool on = [] {
-    const char* v = getenv("NTT_TWO_PASS_24");
-    return v && *v == '1';
-  }();
-  return on;
-}
+// knob::two_pass_24 routes a default 2^24 4-limb plan's single-vector transforms there.
 static void make_wide_plan(std::unique_ptr<PlanBase>& out, const uint64_t* p64, const uint64_t* g64,
                            unsigned limbs64, unsigned log_n, int device, unsigned flags) {
-  if (limbs64 != 4 || !wide_flags_ok(flags) || !wide_tiles_enabled()) return;
+  if (limbs64 != 4 || !wide_flags_ok(flags) || !knob::wide_tiles()) return;
   if (log_n == 24) {
-    if (!two_pass_24_enabled() || (flags & ~NTT_PLAN_MONTGOMERY_IO)) return;
+    if (!knob::two_pass_24() || (flags & ~NTT_PLAN_MONTGOMERY_IO)) return;
   } else if (log_n != 20) {
     return;
   }
   if ((flags & NTT_PLAN_IN_PLACE) && (flags & NTT_PLAN_MONTGOMERY_IO)) return;
   uint32_t p32[12] = {0}, g32[12] = {0};
-  for (unsigned i = 0; i < 4; ++i) {
-    p32[2 * i] = (uint32_t)p64[i];
-    p32[2 * i + 1] = (uint32_t)(p64[i] >> 32);
-    g32[2 * i] = (uint32_t)g64[i];
-    g32[2 * i + 1] = (uint32_t)(g64[i] >> 32);
-  }
+  split_limbs(p32, g32, p64, g64, 4);
   int cur = 0;
   (void)hipGetDevice(&cur);
   if (cur != device) (void)hipSetDevice(device);
   size_t free_b = 0, total_b = 0;
   const bool room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= kWideMinFreeBytes;
   if (room) {
-#if NTT_DEBUG_CHECKS
-    const char* tf = getenv("NTT_TEST_WIDE_FAIL");
-    const bool refuse = tf && tf[0] == '1';
-#else
-    constexpr bool refuse = false;
-#endif
-    if (refuse) {
+    if (knob::test_wide_fail()) {  // checked build only
       void* p = nullptr;
       if (hipMalloc(&p, ~(size_t)0 >> 4) == hipSuccess) (void)hipFree(p);  // refused: the sticky error
     } else {
-      auto impl = std::make_unique<PlanImpl<Eng256T>>();
-      if (impl->init(p32, g32, log_n, device, flags) == NTT_OK &&
+      std::unique_ptr<PlanBase> impl;
+      if (make_impl<Eng256T>(impl, p32, g32, log_n, device, flags) == NTT_OK &&
           (!(flags & NTT_PLAN_SINGLE_LAUNCH) || impl->single_launch_ready()))
         out = std::move(impl);
     }
@@ -2692,16 +1848,8 @@ static std::mutex g_cache_mu;
 static auto& g_cache = *new std::map<std::tuple<std::vector<uint64_t>, std::vector<uint64_t>, unsigned, unsigned, int>,
                                      std::shared_ptr<CachedPlan>>();
 static uint64_t g_cache_tick = 0;
-// At most NTT_SHIM_CACHE_PLANS (default 8) cached plans; the least recently used one is dropped
+// At most knob::shim_cache_plans() (default 8) cached plans; the least recently used one is dropped
 // when a new key arrives (a call still running on it keeps it alive through its shared_ptr).
-static size_t shim_cache_cap() {
-  static const size_t cap = [] {
-    const char* v = getenv("NTT_SHIM_CACHE_PLANS");
-    const long c = v ? atol(v) : 8;
-    return (size_t)(c > 0 ? c : 1);
-  }();
-  return cap;
-}
 
 static std::shared_ptr<CachedPlan> cached_plan(const uint64_t* p, const uint64_t* g, unsigned limbs64, unsigned log_n,
                                                int* rc) {
@@ -2719,7 +1867,7 @@ static std::shared_ptr<CachedPlan> cached_plan(const uint64_t* p, const uint64_t
   ntt_plan* pl = nullptr;
   *rc = ntt_plan_create_custom(&pl, p, g, limbs64, log_n, dev);
   if (*rc != NTT_OK) return nullptr;
-  while (g_cache.size() >= shim_cache_cap()) {
+  while (g_cache.size() >= knob::shim_cache_plans()) {
     auto lru = g_cache.begin();
     for (auto jt = g_cache.begin(); jt != g_cache.end(); ++jt)
       if (jt->second->last_use < lru->second->last_use) lru = jt;
