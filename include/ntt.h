@@ -260,6 +260,38 @@ int ntt_inverse_coset(ntt_plan* plan, void* d_data, const uint64_t* shift, void*
 int ntt_lde_batch(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
                   unsigned batch, void* hip_stream);
 
+/* Transforms over the COLUMNS of a row-major matrix: 2^log_n rows of `width` elements, one polynomial
+ * per column, element (j, b) at d_data[j * width + b] (j < 2^log_n, b < width) -- the layout a STARK
+ * prover keeps a trace or a batch of committed polynomials in, each row of the result being one Merkle
+ * leaf.  A vector over a degree-d extension field, stored as d adjacent base-field coefficients per
+ * element and transformed with base-field twiddles, is such a matrix of d * width columns.  `width` is
+ * any positive number with 2^log_n * width < 2^32; there is no row pitch other than `width`.
+ *   ntt_forward_matrix / ntt_inverse_matrix: every column transformed in place as ntt_forward /
+ *     ntt_inverse would (natural order, canonical elements, 1/n included in the inverse);
+ *   ntt_lde_matrix: `plan` has the LARGE size N = 2^log_n; d_in is [n = N >> log_blowup][width],
+ *     d_out [N][width], out[k][b] = sum_{j < n} in[j][b] (c w_N^k)^j, c = *shift, or 1 when shift == NULL.
+ *     d_in is not modified.  `shift` and its cached tables as ntt_lde_batch.
+ * Asynchronous on hip_stream.  With width == 1 the results are those of ntt_forward / ntt_inverse /
+ * ntt_lde_batch(batch = 1) bit for bit.  NTT_PLAN_MONTGOMERY_IO plans keep their data in Montgomery form
+ * (the transforms are linear); NTT_PLAN_SINGLE_LAUNCH is ignored.
+ * The data are never transposed, padded or staged: every pass reads and writes the matrix (or a plan
+ * scratch of exactly 2^log_n * width elements) once, a workgroup working on a strip of adjacent columns
+ * (at least 64 bytes of every row it touches, the whole row when that is shorter); the zero rows of an
+ * extension are never read or written.  The calls run a schedule of their own
+ * (ntt_plan_matrix_info: its pass count, 0 for sizes up to 4 rows, and log2 radices at this width), whose
+ * tables the plan builds at its first matrix call.
+ * Engines: Goldilocks, BabyBear, KoalaBear and NTT_PLAN_ELEM32 custom plans, at every log_n the plan
+ * accepts.  Plans of fields 0-2 and of custom 4- and 6-limb moduli return NTT_ERR_ARG from all four
+ * calls for now.
+ * NTT_ERR_ARG before any launch: a null plan or pointer, width == 0, 2^log_n * width >= 2^32,
+ * log_blowup > log_n, a bad shift, overlapping byte ranges of d_in and d_out, NTT_PLAN_TWIDDLE_ONLY
+ * plans. */
+int ntt_forward_matrix(ntt_plan* plan, void* d_data, unsigned width, void* hip_stream);
+int ntt_inverse_matrix(ntt_plan* plan, void* d_data, unsigned width, void* hip_stream);
+int ntt_lde_matrix(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
+                   unsigned width, void* hip_stream);
+int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]);
+
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */
 int ntt_pointwise_mul(ntt_plan* plan, const void* d_a, const void* d_b, void* d_c, void* hip_stream);

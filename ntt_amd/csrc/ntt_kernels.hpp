@@ -183,6 +183,11 @@ struct PassArgs {
   // above that length are zero and never loaded (batch_stride stays the destination's stride)
   size_t src_stride;        // 32-bit words between the batch's inputs (n_in * E::MEMW)
   const uint32_t* tw_in_hi; // the shift's two-level hi table (with tw_in = lo_s: c^j at load)
+  // ---- row-major matrix transforms (k_pass_mat, ntt_*_matrix): the pass runs on strips of 2^il adjacent
+  // columns of a [n][mat_w] matrix, element (row, col) at row mat_w + col; workgroup g of the launch is
+  // strip g mod mat_ns of tile g / mat_ns (the strips of one tile share lines: they run together)
+  uint32_t mat_w;   // columns of the matrix
+  uint32_t mat_ns;  // strips per row: ceil(mat_w / 2^il)
 };
 enum : uint32_t { FS_MAP_IN = 1u, FS_MAP_OUT = 2u, FS_IL = 4u, FS_MAP_EPI = 8u };
 
@@ -282,6 +287,38 @@ hipError_t launch_lde_scale(const uint32_t* src, uint32_t* dst, size_t n_in, uin
 template <class E>
 hipError_t launch_lde_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
                            uint32_t batch, hipStream_t st);
+// ---- row-major matrix transforms (ntt_forward_matrix / ntt_inverse_matrix / ntt_lde_matrix): the
+// transforms run over the columns of a [n][width] matrix in the strip form of the pass tile (MAT in
+// ntt_kernels_impl.hpp).  Engines with instances (ntt_eg_mat.hip, ntt_e31_mat.hip): the two a STARK
+// prover's plans run on; nothing is instantiated for the others.
+template <class E>
+struct HasMat {
+  static constexpr bool value = std::is_same_v<E, Eng64G> || std::is_same_v<E, Eng31>;
+};
+// A strip is at least 64 contiguous bytes per row (half a 128-byte line): 2^4 columns of 4 B, 2^3 of 8 B
+template <class E>
+__host__ __device__ constexpr int mat_min_strip_log() {
+  return E::MEMW == 1 ? 4 : 3;
+}
+// ... which caps a matrix pass's radix at TILE >> that (2^9 on both engines)
+template <class E>
+__host__ __device__ constexpr int mat_max_radix_log() {
+  return E::TILE_LOG - mat_min_strip_log<E>();
+}
+// One pass of a matrix transform: kind = KIND_COLUMN (two-level outer twiddles; a transform of one pass
+// is a column pass whose columns are the strip's: its outer twiddles are w^0, its output natural) or
+// KIND_FINAL; 3 <= logr <= mat_max_radix_log.  A.il = log2 of the strip's columns, A.mat_w, A.mat_ns set;
+// grid = tiles x strips workgroups.  lde: the pass reads the first A.src_stride / E::MEMW rows only and
+// multiplies row j by c^j at the load (A.tw_in / A.tw_in_hi, null: no shift); KIND_COLUMN only.
+template <class E>
+hipError_t launch_mat_pass(int kind, int logr, bool lde, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A,
+                           uint32_t grid, hipStream_t st);
+// Matrix transforms of 2 and 4 rows, O(n^2): out[k][b] = sum_{j < n_in} in[j][b] c^j w^(jk), times n^-1
+// when A.flags bit 0; A.tw_int holds w^e (e < n), A.tw_in / A.tw_in_hi the shift's tables or null.
+// src == dst is allowed when n_in = n (each thread owns one column).
+template <class E>
+hipError_t launch_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t n_in, hipStream_t st);
+
 template <class E>
 hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,
                            const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F,

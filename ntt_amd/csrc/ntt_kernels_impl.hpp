@@ -481,8 +481,14 @@ __host__ __device__ constexpr bool pass_ltw() {
 // has been read.  2 / 3 (k_fused3bi / k_fused2bi, every final tile resident): a grid barrier between
 // all loads and all stores.  4 (pass 1 of k_fused3bi / k_fused2bi): the stores wait for the launch's
 // residency decision (residency_wait) and are skipped when it was abandoned.
+// MAT (k_pass_mat, the ntt_*_matrix calls): the strip form.  The tile is Mode I with il = A.il on strip
+// bq of a row-major [n][A.mat_w] matrix: (TILE >> il) transform positions by 2^il adjacent columns, the
+// interleaved index P = row 2^il + bl standing for element (row, bq 2^il + bl) at row A.mat_w + that
+// column -- a multiply where Mode I shifts.  Twiddle indices depend on the row alone.  Columns at and
+// past A.mat_w (the last strip of a row) do not exist: their lanes load nothing, carry zeros through
+// the tile and store nothing.
 template <class E, int LOGR, int KIND, bool FULLTW, bool FAST, int PRO = PRO_NONE, bool SRC_USER = true,
-          int FSM = 0, bool SHTW = false, bool WT = false, bool LOOPED = false, int IPN = 0>
+          int FSM = 0, bool SHTW = false, bool WT = false, bool LOOPED = false, int IPN = 0, bool MAT = false>
 __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                           const PassArgs<E>& A, const uint32_t w, const uint32_t bq,
                                           uint32_t* __restrict__ lds, uint32_t* __restrict__ lds_tw) {
@@ -513,14 +519,16 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
   // are kernel arguments (wave-uniform branches); fs == 0 is the plain batched transform.
   constexpr bool IN_USER = (KIND == KIND_COLUMN && SRC_USER) || KIND == KIND_SINGLE || ROWS;
   constexpr bool EPI = FSM == 2 && KIND != KIND_COLUMN;
-  const bool fs_il = FSM > 0 && (A.fs & FS_IL) != 0;
-  const bool map_in = FSM > 0 && IN_USER && (A.fs & FS_MAP_IN);
-  const bool map_out = FSM > 0 && KIND != KIND_COLUMN && (A.fs & FS_MAP_OUT);
+  static_assert(!MAT || ((KIND == KIND_COLUMN || KIND == KIND_FINAL) && FSM == 1 && !FULLTW && IPN == 0), "strip form");
+  const bool fs_il = MAT || (FSM > 0 && (A.fs & FS_IL) != 0);
+  const bool map_in = !MAT && FSM > 0 && IN_USER && (A.fs & FS_MAP_IN);
+  const bool map_out = !MAT && FSM > 0 && KIND != KIND_COLUMN && (A.fs & FS_MAP_OUT);
   // one interleaved transform per workgroup (KIND_ROWS: T adjacent ones, runs of T elements)
   const bool single_il = (KIND == KIND_SINGLE || ROWS) && fs_il;
   const size_t tstride = A.batch_stride / E::MEMW;  // elements between batched transforms
-  const size_t bidx = (size_t)bq * tstride;         // first element of this transform (KIND_ROWS: bq = 0)
-  if constexpr (PRO == PRO_LDE) src += (size_t)bq * A.src_stride;  // the inputs are shorter than the outputs
+  const size_t bidx = MAT ? 0 : (size_t)bq * tstride;  // first element of this transform (KIND_ROWS: bq = 0; MAT: bq is the strip)
+  if constexpr (MAT) {}
+  else if constexpr (PRO == PRO_LDE) src += (size_t)bq * A.src_stride;  // the inputs are shorter than the outputs
   else if (!map_in && !single_il) src += bidx * SW;
   if (!map_out && !single_il) dst += bidx * DW;
   const size_t boff = bidx * E::MEMW;  // caller-buffer words (src2)
@@ -543,6 +551,12 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
     if (!fs_il) return (b << A.log_n) + pos;
     if (single_il) pos = (pos << A.il) + b;
     return (A.fs & FS_MAP_EPI) ? A.mepi(pos, 0) : pos;
+  };
+  // MAT: the address of interleaved index P of this strip; false: the column does not exist
+  auto mat_at = [&](size_t P, size_t& at) -> bool {
+    const uint32_t col = (bq << A.il) + (uint32_t)(P & ((1u << A.il) - 1));
+    at = (P >> A.il) * A.mat_w + col;
+    return col < A.mat_w;
   };
   // debug builds: an index outside its buffer is recorded and redirected to element 0
   auto ck = [&](size_t i, [[maybe_unused]] size_t lim) -> size_t {
@@ -639,12 +653,19 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
         }
         const size_t b = ROWS ? (size_t)w * T + c : (size_t)bq;  // this element's transform
         if constexpr (PRO == PRO_LDE) {
-          static_assert(FSM == 0 && SRC_USER && (KIND == KIND_SINGLE || KIND == KIND_COLUMN), "PRO_LDE passes");
-          // pos is the position in the transform (pass 1 has one block).  Zeros past the input's end
-          // come from registers; a tile with no input at all still runs and stores its zeros over
-          // whatever the scratch or the caller's buffer held.
-          if (pos < A.src_stride / E::MEMW) {
-            E::template load<SW>(x[j * Q + d], src, ck(pos, A.dbg_src_n));
+          static_assert((FSM == 0 || MAT) && SRC_USER && (KIND == KIND_SINGLE || KIND == KIND_COLUMN), "PRO_LDE passes");
+          // pos is the position in the transform (pass 1 has one block; MAT: row 2^il + bl, the input
+          // being the matrix's first rows).  Zeros past the input's end come from registers; a tile with
+          // no input at all still runs and stores its zeros over whatever the scratch or the caller's
+          // buffer held.
+          size_t at = pos;
+          bool have = true;
+          if constexpr (MAT) {
+            have = mat_at(pos, at);
+            pos >>= A.il;  // the row: c^row below
+          }
+          if (have && pos < A.src_stride / E::MEMW) {
+            E::template load<SW>(x[j * Q + d], src, ck(at, A.dbg_src_n));
 #if NTT_DEBUG_CHECKS
             if (!E::dbg_canonical(x[j * Q + d], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
 #endif
@@ -663,6 +684,19 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
                 E::mulv(x[j * Q + d], tl.w, A.F);
               }
             }
+          } else {
+#pragma unroll
+            for (int l = 0; l < E::W; ++l) x[j * Q + d][l] = 0u;
+          }
+        } else if constexpr (MAT) {
+          size_t at;
+          if (mat_at(pos, at)) {
+            E::template load<SW>(x[j * Q + d], src, ck(at, A.dbg_src_n));
+#if NTT_DEBUG_CHECKS
+            if (KIND == KIND_COLUMN && A.src_user) {
+              if (!E::dbg_canonical(x[j * Q + d], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
+            }
+#endif
           } else {
 #pragma unroll
             for (int l = 0; l < E::W; ++l) x[j * Q + d][l] = 0u;
@@ -792,7 +826,12 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
             E::mulv(v, tl.w, A.F);
           }
           pos = colbase + c + ((size_t)kn << log_s);
-          E::template store_lazy<E::MUL_OUT, FAST, DW, WT>(dst, ck(pos, A.dbg_dst_n), v, A.F);  // scratch: < 2p, read by the next pass
+          if constexpr (MAT) {  // scratch (or, for a transform of one pass, the caller's buffer) in the matrix's own layout
+            size_t at;
+            if (mat_at(pos, at)) E::template store_lazy<E::MUL_OUT, FAST, DW, WT>(dst, ck(at, A.dbg_dst_n), v, A.F);
+          } else {
+            E::template store_lazy<E::MUL_OUT, FAST, DW, WT>(dst, ck(pos, A.dbg_dst_n), v, A.F);  // scratch: < 2p, read by the next pass
+          }
         } else if constexpr (KIND == KIND_FINAL) {
           if (fs_il) {
             const uint32_t k1 = k10 + (c >> tb_log), b = b0 + (c & ((1u << tb_log) - 1));
@@ -807,6 +846,9 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
             E::template load<E::TABW>(tw, A.tw_epi, epi_idx(pos, bq));
             E::mulv(v, tw, A.F);
             E::template store<E::MUL_OUT, FAST, DW>(dst, ck(out_pos(pos, bq), A.dbg_dst_n), v, A.F);
+          } else if constexpr (MAT) {
+            size_t at;
+            if (mat_at(pos, at)) E::template store<E::IN * Q, FAST, DW>(dst, ck(at, A.dbg_dst_n), v, A.F);
           } else {
             E::template store<E::IN * Q, FAST, DW>(dst, ck(out_pos(pos, bq), A.dbg_dst_n), v, A.F);
           }
@@ -2384,6 +2426,124 @@ hipError_t launch_lde_pass(int kind, int logr, const uint32_t* src, uint32_t* ds
   return hipErrorInvalidValue;
 }
 
+// ---------------------------------------------------------------------------- row-major matrix passes
+// One pass over the columns of a row-major matrix (pass_tile's strip form, MAT): workgroup g runs strip
+// g mod A.mat_ns of tile g / A.mat_ns, so the strips of one tile -- which share the lines that a row
+// boundary or a strip boundary cuts -- are dispatched together.  One scalar division per workgroup.
+template <class E, int LOGR, int KIND, int PRO>
+__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
+void k_pass_mat(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const PassArgs<E> A) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[pass_lds_words<E, LOGR, KIND>()];
+  __shared__ __attribute__((aligned(16))) uint32_t lds_tw[pass_ltw<E, KIND, false>() ? (1 << LOGR) * E::TW : 1];
+  const uint32_t w = blockIdx.x / A.mat_ns, strip = blockIdx.x - w * A.mat_ns;
+  pass_tile<E, LOGR, KIND, false, false, PRO, true, 1, false, false, false, 0, true>(src, dst, A, w, strip, lds, lds_tw);
+}
+
+template <class E, int LOGR>
+static hipError_t launch_mat_r(int kind, bool lde, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A,
+                               uint32_t grid, hipStream_t st) {
+  if constexpr (!HasMat<E>::value || LOGR > mat_max_radix_log<E>()) {
+    return hipErrorInvalidValue;
+  } else {
+    static_assert(!E::FASTRED && lde_mul_at_load<E, KIND_COLUMN>(), "matrix engines");
+    const dim3 g(grid), b((1 << E::TILE_LOG) / E::EPT);
+    // the strip is no wider than the tile's columns (column pass) or blocks (final pass), and no narrower
+    // than the 64-byte rule allows
+    if (A.mat_w == 0 || A.mat_ns == 0 || A.il + LOGR > (uint32_t)E::TILE_LOG || A.fs || A.tw_epi || A.src2 ||
+        A.tw_full || A.tw_sh)
+      return hipErrorInvalidValue;
+    if (kind == KIND_COLUMN && lde) {
+      if (A.src_stride == 0) return hipErrorInvalidValue;
+      hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_COLUMN, PRO_LDE>), g, b, 0, st, src, dst, A);
+    } else if (lde || A.tw_in) {
+      return hipErrorInvalidValue;
+    } else if (kind == KIND_COLUMN) {
+      hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_COLUMN, PRO_NONE>), g, b, 0, st, src, dst, A);
+    } else if (kind == KIND_FINAL) {
+      hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_FINAL, PRO_NONE>), g, b, 0, st, src, dst, A);
+    } else {
+      return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
+}
+
+template <class E>
+hipError_t launch_mat_pass(int kind, int logr, bool lde, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A,
+                           uint32_t grid, hipStream_t st) {
+  switch (logr) {
+    case 3: return launch_mat_r<E, 3>(kind, lde, src, dst, A, grid, st);
+    case 4: return launch_mat_r<E, 4>(kind, lde, src, dst, A, grid, st);
+    case 5: return launch_mat_r<E, 5>(kind, lde, src, dst, A, grid, st);
+    case 6: return launch_mat_r<E, 6>(kind, lde, src, dst, A, grid, st);
+    case 7: return launch_mat_r<E, 7>(kind, lde, src, dst, A, grid, st);
+    case 8: return launch_mat_r<E, 8>(kind, lde, src, dst, A, grid, st);
+    case 9: return launch_mat_r<E, 9>(kind, lde, src, dst, A, grid, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// Matrix transforms of 2 and 4 rows: a thread per column holds the column's inputs in registers (so
+// src may be dst) and forms the n outputs as k_dft_naive does.
+template <class E>
+__global__ void k_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E> A, uint32_t n_in) {
+  const uint32_t n = 1u << A.log_n;
+  NTT_GRID_STRIDE(b, A.mat_w) {
+    uint32_t x[4][E::W];
+    static_for<4>([&](auto J) {
+      constexpr int j = J;
+      if (j < n_in) {
+        E::load(x[j], src, (size_t)j * A.mat_w + b);
+#if NTT_DEBUG_CHECKS
+        if (!E::dbg_canonical(x[j], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
+#endif
+        if (A.tw_in) {  // c^j from the shift's two-level tables
+          typename E::Tw tl, th;
+          E::tload(tl, A.tw_in, (uint32_t)(j & ((1u << A.lo_bits) - 1)));
+          E::tload(th, A.tw_in_hi, (uint32_t)(j >> A.lo_bits));
+          E::mul(tl.w, th, A.F);
+          E::mulv(x[j], tl.w, A.F);
+        }
+      }
+    });
+    static_for<4>([&](auto K) {
+      constexpr int k = K;
+      if (k < n) {
+        uint32_t acc[E::W], v[E::W];
+        typename E::Tw w;
+#pragma unroll
+        for (int l = 0; l < E::W; ++l) acc[l] = x[0][l];
+        E::tload(w, A.tw_int, 0);
+        E::mul(acc, w, A.F);
+        static_for<3>([&](auto J1) {
+          constexpr int j = J1 + 1;
+          if (j < n_in) {
+#pragma unroll
+            for (int l = 0; l < E::W; ++l) v[l] = x[j][l];
+            E::tload(w, A.tw_int, (j * k) & (n - 1));
+            E::mul(v, w, A.F);
+            E::template bfly_l<E::IN>(acc, v, A.F);  // acc <- acc + v (the difference is discarded)
+            E::template reduce<2 * E::IN, E::IN>(acc, A.F);
+          }
+        });
+        if (A.flags & 1u) E::mul(acc, A.F.ninv, A.F);
+        E::template store<E::IN>(dst, (size_t)k * A.mat_w + b, acc, A.F);
+      }
+    });
+  }
+}
+
+template <class E>
+hipError_t launch_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t n_in, hipStream_t st) {
+  if constexpr (!HasMat<E>::value) {
+    return hipErrorInvalidValue;
+  } else {
+    if (A.log_n < 1 || A.log_n > 2 || n_in == 0 || n_in > (1u << A.log_n) || A.mat_w == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_mat_naive<E>), dim3(grid_1d(A.mat_w)), dim3(256), 0, st, src, dst, A, n_in);
+    return hipGetLastError();
+  }
+}
+
 template <class E>
 hipError_t launch_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t batch, hipStream_t st) {
   hipLaunchKernelGGL((k_dft_naive<E>), dim3(1, batch), dim3(64), 0, st, src, dst, A);
@@ -2427,7 +2587,13 @@ hipError_t launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* c, s
   template hipError_t launch_lde_scale<E>(const uint32_t*, uint32_t*, size_t, uint32_t, const uint32_t*,       \
                                           const uint32_t*, uint32_t, const typename E::Args&, hipStream_t);
 
-#define NTT_INSTANTIATE_FUSED(E)                                                                                 \
+// The row-major matrix passes of one engine (a translation unit of their own: ntt_*_mat.hip)
+#define NTT_INSTANTIATE_MAT(E)                                                                                 \
+  template hipError_t launch_mat_pass<E>(int, int, bool, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
+                                         hipStream_t);                                                         \
+  template hipError_t launch_mat_naive<E>(const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, hipStream_t);
+
+#define NTT_INSTANTIATE_FUSED(E)                                                                                \
   template hipError_t launch_fused3<E>(int, int, int, const uint32_t*, uint32_t*, uint32_t*, const PassArgs<E>&,     \
                                        const PassArgs<E>&, const PassArgs<E>&, const FusedArgs&, hipStream_t);      \
   template hipError_t fused3_capacity<E>(int, int, int, int, uint32_t*, uint32_t);

@@ -89,6 +89,11 @@ struct PlanBase {
   // low-degree extension (ntt_lde_batch): batch inputs of n >> log_blowup coefficients to batch outputs of n
   virtual int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* shift, unsigned limbs64,
                   unsigned batch, hipStream_t st) = 0;
+  // the columns of a row-major [n][width] matrix (ntt_forward_matrix / ntt_inverse_matrix: in == out;
+  // ntt_lde_matrix: is_lde, in = [n >> log_blowup][width]) and the schedule those calls run
+  virtual int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
+                     const uint64_t* shift, unsigned limbs64, hipStream_t st) = 0;
+  virtual int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -300,6 +305,8 @@ struct PlanImpl final : PlanBase {
     };
     fill_args(Ff, w);
     fill_args(Fi, winv);
+    wn_m[0] = w;
+    wn_m[1] = winv;
 
     // random-fill parameters: top nonzero 64-bit limb of p, masked to bitlen-1 bits
     {
@@ -699,6 +706,134 @@ struct PlanImpl final : PlanBase {
                                        Ff, st) != hipSuccess)
       return NTT_ERR_HIP;
     return run_io(dst, nullptr, dst, batch, false, st);
+  }
+
+  // ---- row-major matrix transforms (ntt_forward_matrix / ntt_inverse_matrix / ntt_lde_matrix): the
+  // transforms run down the columns of a [n][width] matrix on a schedule of their own (plan_schedule.hpp
+  // schedule_matrix: radices up to TILE >> strip, a strip of columns per pass), every pass in the strip
+  // form of the pass tile (k_pass_mat).  Column passes take their outer twiddles from the plan's
+  // two-level tables; the w_R^e tables of the matrix radices are built at the first matrix call.
+  Vec<NH> wn_m[2];              // w_n, w_n^-1 (Montgomery form), for tables built after init
+  Lazy mat_state;               // ready: d_mat_tab holds the tables below
+  DevBuf d_mat_tab;
+  unsigned mat_r[8] = {0}, mat_p = 0;
+  size_t mat_int[2][8] = {};    // [dir][pass]: word offset of w_{R_i}^e (naive sizes: pass 0 = w_n^e, e < n)
+  bool build_mat() {
+    unsigned tb[8];
+    if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), 1, mat_r, tb, mat_p)) return false;
+    std::vector<uint32_t> host;
+    for (int dir = 0; dir < 2; ++dir) {
+      if (mat_p == 0) mat_int[dir][0] = push_powers_to(host, wn_m[dir], n, nullptr, false);
+      for (unsigned i = 0; i < mat_p; ++i)
+        mat_int[dir][i] = push_powers_to(host, H.pow_u64(wn_m[dir], n >> mat_r[i]), 1ull << mat_r[i], nullptr, false);
+    }
+    return d_mat_tab.alloc(host.size() * 4) &&
+           hipMemcpy(d_mat_tab.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const override {
+    if constexpr (!HasMat<E>::value) {
+      return NTT_ERR_ARG;
+    } else {
+      unsigned rr[8] = {0}, tb[8], p = 0;
+      if (width == 0 || ((uint64_t)n * width) >> 32 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
+      if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), width, rr, tb, p)) return NTT_ERR_ARG;
+      if (npasses) *npasses = p;
+      if (radix_log)
+        for (int i = 0; i < 8; ++i) radix_log[i] = rr[i];
+      return NTT_OK;
+    }
+  }
+  // in: [n_in = n >> log_blowup][width] (is_lde) or the matrix itself (in == out); out: [n][width]
+  int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
+             const uint64_t* shift, unsigned limbs64, hipStream_t st) override {
+    if constexpr (!HasMat<E>::value) {
+      return NTT_ERR_ARG;
+    } else {
+      if (!in || !out || width == 0 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
+      if (((uint64_t)n * width) >> 32) return NTT_ERR_ARG;  // element indices are 32-bit in places
+      if (is_lde && log_blowup > log_n) return NTT_ERR_ARG;
+      const size_t n_in = is_lde ? (size_t)(n >> log_blowup) : (size_t)n, eb = (size_t)MEMW * 4;
+      if (is_lde) {
+        const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * width * eb;
+        const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)n * width * eb;
+        if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // the first pass reads d_in while later tiles write d_out
+        if (shift)
+          if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
+      }
+      unsigned tb[8] = {0}, rr[8], p = 0;
+      if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), width, rr, tb, p)) return NTT_ERR_ARG;
+      if (!mat_state.ready([&] { return build_mat(); })) return NTT_ERR_HIP;
+      const uint32_t* src = static_cast<const uint32_t*>(in);
+      uint32_t* dst = static_cast<uint32_t*>(out);
+      if (log_n == 0) {  // one row: the transform of one point, c^0 = 1
+        if (dst != src && hipMemcpyAsync(dst, src, width * eb, hipMemcpyDeviceToDevice, st) != hipSuccess) return NTT_ERR_HIP;
+        return NTT_OK;
+      }
+      const int dir = inverse ? 1 : 0;
+      const bool shifted = is_lde && shift;
+      auto mat_args = [&](unsigned i) {
+        PassArgs<E> A = base_args(inverse);
+        A.tw_int = d_mat_tab.get() + mat_int[dir][i];
+        A.mat_w = width;
+        A.il = tb[i];
+        A.mat_ns = (uint32_t)(((uint64_t)width + (1u << tb[i]) - 1) >> tb[i]);
+        A.dbg_src_n = A.dbg_dst_n = (size_t)n * width;
+        if (i == 0 && is_lde) {
+          A.src_stride = n_in * MEMW;
+          A.dbg_src_n = n_in * width;
+          if (shifted) {
+            A.tw_in = d_coset.get() + coset_off[0][0];
+            A.tw_in_hi = d_coset.get() + coset_off[0][1];
+          }
+        }
+        return A;
+      };
+      hipError_t e = hipSuccess;
+      begin(st);
+      if (mat_p == 0) {
+        PassArgs<E> A = mat_args(0);
+        A.flags = inverse ? 1u : 0u;
+        e = launch_mat_naive<E>(src, dst, A, (uint32_t)n_in, st);
+        mark(st, "n");
+        return rc_of(e);
+      }
+      uint32_t* work = dst;
+      if (mat_p >= 2) {  // n width elements, not the next power of two
+        if (!d_scratch.grow((size_t)n * width * SCRW * 4)) return NTT_ERR_HIP;
+        work = d_scratch.get();
+      }
+      unsigned blk = log_n;
+      const unsigned ncol = mat_p == 1 ? 1 : mat_p - 1;  // column passes (a transform of one pass is one)
+      for (unsigned i = 0; i < ncol && e == hipSuccess; ++i) {
+        PassArgs<E> A = mat_args(i);
+        A.tw_lo = outer_lo(dir);
+        A.tw_hi = outer_hi(dir, i);  // the inverse's pass 1 carries n^-1
+        A.log_blk = blk + tb[i];
+        A.log_m = log_n - blk;
+        A.src_user = i == 0 ? 1u : 0u;
+        const uint32_t grid = (uint32_t)(((n << tb[i]) >> E::TILE_LOG) * A.mat_ns);
+        e = launch_mat_pass<E>(KIND_COLUMN, (int)mat_r[i], i == 0 && is_lde, i == 0 ? src : work, work, A, grid, st);
+        mark(st, mat_p == 1 ? "s" : "c", mat_r[i]);
+        blk -= mat_r[i];
+      }
+      if (mat_p >= 2 && e == hipSuccess) {
+        const unsigned i = mat_p - 1;
+        PassArgs<E> A = mat_args(i);
+        A.r1 = mat_r[0];
+        A.nmid = mat_p - 2;
+        for (unsigned m = 0; m < A.nmid; ++m) {  // middle digits, least significant first (pass_args)
+          const unsigned idx = mat_p - 2 - m;
+          A.mid_bits[m] = mat_r[idx];
+          unsigned off = 0;
+          for (unsigned j = 1; j < idx; ++j) off += mat_r[j];
+          A.mid_off[m] = off;
+        }
+        const uint32_t grid = (uint32_t)(((n << tb[i]) >> E::TILE_LOG) * A.mat_ns);
+        e = launch_mat_pass<E>(KIND_FINAL, (int)mat_r[i], false, work, dst, A, grid, st);
+        mark(st, "f", mat_r[i]);
+      }
+      return rc_of(e);
+    }
   }
 
   // the engine's fast (quotient-estimate) reduction holds for this modulus in direction F
@@ -1644,6 +1779,29 @@ int ntt_lde_batch(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_bl
     const unsigned limbs64 = P.elem_bytes >= 32 ? P.elem_bytes / 8 : 1;
     return P.lde(d_in, d_out, log_blowup, shift, limbs64, batch, S(s));
   });
+}
+
+// Row-major matrix transforms: the plan's own engine on the matrix schedule (never the second plan)
+static int run_matrix(ntt_plan* plan, const void* in, void* out, unsigned width, bool inverse, bool is_lde,
+                      unsigned log_blowup, const uint64_t* shift, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.matrix(in, out, width, inverse, is_lde, log_blowup, shift, 1, S(s));
+  });
+}
+int ntt_forward_matrix(ntt_plan* plan, void* d, unsigned width, void* s) {
+  return run_matrix(plan, d, d, width, false, false, 0, nullptr, s);
+}
+int ntt_inverse_matrix(ntt_plan* plan, void* d, unsigned width, void* s) {
+  return run_matrix(plan, d, d, width, true, false, 0, nullptr, s);
+}
+int ntt_lde_matrix(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
+                   unsigned width, void* s) {
+  return run_matrix(plan, d_in, d_out, width, false, true, log_blowup, shift, s);
+}
+int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
+  if (!plan || !plan->impl) return NTT_ERR_ARG;
+  return plan->impl->matrix_info(width, npasses, radix_log);
 }
 
 int ntt_pointwise_mul(ntt_plan* plan, const void* a, const void* b, void* c, void* s) {

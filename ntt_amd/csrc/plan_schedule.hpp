@@ -105,6 +105,48 @@ static bool schedule_for(unsigned log_n, unsigned tile_log, unsigned min_cols_lo
   return true;
 }
 
+// The schedule of the row-major matrix calls (ntt_*_matrix): the transforms run down the columns of a
+// [n][width] matrix, a workgroup's tile being (TILE >> tb) transform positions by a strip of 2^tb
+// adjacent columns.  Every global access is then a run of 2^tb elements per row, and the rule is that a
+// run is at least 64 bytes (half a line): tb >= strip_log (2^4 columns of 4 B, 2^3 of 8 B), so a radix
+// is at most tile_log - strip_log.  The batched schedule does not serve: it puts up to a whole tile of
+// one transform in a workgroup, which here is one element per row.
+//   * log_n <= 2: p = 0 (the naive kernel);
+//   * else p = ceil(log_n / rmax) passes, the near-equal split in ascending order (each radix >= 3
+//     since rmax >= 6); p = 1 is a column pass over the strip's columns alone.
+// tb[i], the strip of pass i, may differ between passes (the addresses do not depend on it).  Its range:
+// the tile's columns hold a strip (tb <= tile_log - r_i); a column pass's block spans a tile
+// (log N_i + tb >= tile_log); the final pass's blocks fit in R_1 (r_1 + r_p + tb >= tile_log).  Within
+// the range, the tb whose strips cover the row with the fewest masked columns, the smallest such.
+static bool schedule_matrix(unsigned log_n, unsigned tile_log, unsigned strip_log, unsigned width, unsigned* r,
+                            unsigned* tb, unsigned& p) {
+  const unsigned rmax = tile_log - strip_log;
+  if (rmax < 6 || width == 0) return false;
+  if (log_n <= 2) { p = 0; return true; }
+  p = (log_n + rmax - 1) / rmax;
+  if (p > 8) return false;
+  const unsigned base = log_n / p, rem = log_n % p;
+  for (unsigned i = 0; i < p; ++i) r[i] = base + (i + rem >= p ? 1 : 0);
+  unsigned blk = log_n;  // log N_i
+  for (unsigned i = 0; i < p; ++i) {
+    const bool final_pass = p >= 2 && i + 1 == p;
+    const unsigned span = final_pass ? r[0] + r[p - 1] : blk;
+    unsigned lo = span >= tile_log ? 0 : tile_log - span;
+    if (lo < strip_log) lo = strip_log;
+    const unsigned hi = tile_log - r[i];
+    if (lo > hi) return false;
+    unsigned best = lo;
+    unsigned long long best_cols = ~0ull;
+    for (unsigned t = lo; t <= hi; ++t) {
+      const unsigned long long cols = (((unsigned long long)width + (1ull << t) - 1) >> t) << t;
+      if (cols < best_cols) best_cols = cols, best = t;
+    }
+    tb[i] = best;
+    blk -= r[i];
+  }
+  return true;
+}
+
 // NTT_PLAN_IN_PLACE: a palindromic sequence (r_i = r_{p-1-i}, 3 <= r_i <= rmax, schedule_ok) with the
 // fewest passes (>= p0), then the smallest largest radix, then the largest smallest one.  The digit
 // reversal of a palindromic sequence is an involution (k_digitrev_swap).

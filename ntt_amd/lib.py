@@ -50,6 +50,10 @@ PROTOTYPES = {
     "ntt_forward_coset": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _vp]),
     "ntt_inverse_coset": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _vp]),
     "ntt_lde_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
+    "ntt_forward_matrix": (C.c_int, [_vp, _vp, C.c_uint, _vp]),
+    "ntt_inverse_matrix": (C.c_int, [_vp, _vp, C.c_uint, _vp]),
+    "ntt_lde_matrix": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
+    "ntt_plan_matrix_info": (C.c_int, [_vp, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "ntt_polymul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ntt_fill": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _vp]),
     "ntt_plan_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_uint),

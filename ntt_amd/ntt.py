@@ -23,7 +23,7 @@ import torch
 from . import lib as _L
 from .fields import FIELDS, field_params
 
-__all__ = ["NTTPlan", "SSIP", "NTT_GZKP", "lde_from_evals", "to_device", "from_device", "FIELDS"]
+__all__ = ["NTTPlan", "SSIP", "NTT_GZKP", "lde_from_evals", "lde_matrix_from_evals", "to_device", "from_device", "FIELDS"]
 
 
 def _stream_ptr(stream, device) -> C.c_void_p:
@@ -277,6 +277,79 @@ class NTTPlan:
                  "ntt_lde_batch")
         return out
 
+    # -------------------------------------------------------------------------------- row-major matrices
+    def _check_matrix(self, t: torch.Tensor, rows: int, width: int, what: str) -> None:
+        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if self.n * width >= 1 << 32:
+            raise ValueError(f"2^log_n * width must stay below 2^32, not {self.n} * {width}")
+        if not t.is_contiguous() or t.dtype != self.dtype:
+            raise ValueError(f"{what} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the "
+                             "plan's element layout")
+        if t.numel() * t.element_size() != rows * width * self.elem_bytes:
+            raise ValueError(f"{what}: expected {rows} rows of {width} elements of {self.elem_bytes} bytes")
+
+    def _check_matrix_device(self, t: torch.Tensor, what: str) -> None:
+        if not t.is_cuda:
+            raise ValueError(f"{what} must be a device (HIP) tensor")
+        if t.device.index != self.device:
+            raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
+
+    def forward_matrix(self, t: torch.Tensor, width: int, stream=None) -> torch.Tensor:
+        """Forward NTT of every column of the row-major matrix ``t`` = [n][width] in place
+        (ntt_forward_matrix): element (j, b) at ``t.view(-1)[j * width + b]``."""
+        self._check_matrix(t, self.n, width, "t")
+        self._check_matrix_device(t, "t")
+        _L.check(self._lib.ntt_forward_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
+                                              _stream_ptr(stream, t.device)), "ntt_forward_matrix")
+        return t
+
+    def inverse_matrix(self, t: torch.Tensor, width: int, stream=None) -> torch.Tensor:
+        """Inverse NTT (1/n included) of every column of the row-major matrix ``t`` = [n][width] in place."""
+        self._check_matrix(t, self.n, width, "t")
+        self._check_matrix_device(t, "t")
+        _L.check(self._lib.ntt_inverse_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
+                                              _stream_ptr(stream, t.device)), "ntt_inverse_matrix")
+        return t
+
+    def _check_lde_matrix(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int],
+                          width: int) -> None:
+        if not isinstance(log_blowup, int) or not 0 <= log_blowup <= self.log_n:
+            raise ValueError(f"log_blowup must be an integer in [0, {self.log_n}], not {log_blowup!r}")
+        if shift is not None and not 0 < int(shift) < self.p:
+            raise ValueError("shift must be canonical and nonzero (0 < shift < p)")
+        n_in = self.n >> log_blowup
+        self._check_matrix(coeffs, n_in, width, "coeffs")
+        self._check_matrix(out, self.n, width, "out")
+        a0, b0 = coeffs.data_ptr(), out.data_ptr()
+        if a0 < b0 + self.n * width * self.elem_bytes and b0 < a0 + n_in * width * self.elem_bytes:
+            raise ValueError("coeffs and out overlap")
+        self._check_matrix_device(coeffs, "coeffs")
+        self._check_matrix_device(out, "out")
+
+    def lde_matrix(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int] = None,
+                   width: int = 1, stream=None) -> torch.Tensor:
+        """Low-degree extension of the columns of a row-major matrix (ntt_lde_matrix).  This plan has the
+        LARGE size N = 2^log_n; ``coeffs`` = [N >> log_blowup][width] holds one polynomial per column,
+        ``out`` = [N][width] receives out[k][b] = sum_j coeffs[j][b] (shift w_N^k)^j (shift None: 1).
+        ``coeffs`` is not modified and must not overlap ``out``."""
+        self._check_lde_matrix(coeffs, out, log_blowup, shift, width)
+        sh = None if shift is None else _u64_array(int_to_limbs(int(shift), self.limbs64))
+        _L.check(self._lib.ntt_lde_matrix(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
+                                          int(log_blowup), sh, int(width), _stream_ptr(stream, out.device)),
+                 "ntt_lde_matrix")
+        return out
+
+    def matrix_passes(self, width: int) -> List[int]:
+        """log2 radices of the passes the matrix calls run at this width (ntt_plan_matrix_info); [] for
+        sizes up to 4 rows, which one simple kernel transforms."""
+        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        npass = C.c_uint()
+        radix = (C.c_uint * 8)()
+        _L.check(self._lib.ntt_plan_matrix_info(self._h, int(width), C.byref(npass), radix), "ntt_plan_matrix_info")
+        return [radix[i] for i in range(npass.value)]
+
     def pointwise_mul(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, stream=None) -> torch.Tensor:
         for t in (a, b, out):
             self._check_tensor(t)
@@ -388,6 +461,22 @@ def lde_from_evals(small_plan: NTTPlan, big_plan: NTTPlan, evals: torch.Tensor, 
     big_plan._check_lde(evals, out, big_plan.log_n - small_plan.log_n, shift, batch)
     small_plan.inverse_batch(evals, batch, stream=stream)
     return big_plan.lde_batch(evals, out, big_plan.log_n - small_plan.log_n, shift, batch, stream=stream)
+
+
+def lde_matrix_from_evals(small_plan: NTTPlan, big_plan: NTTPlan, evals: torch.Tensor, out: torch.Tensor,
+                          shift: Optional[int] = None, width: int = 1, stream=None) -> torch.Tensor:
+    """The matrix form of ``lde_from_evals``: ``evals`` = [n][width] row-major, the evaluations of one
+    polynomial per column on <w_n> (``small_plan``'s size) -> ``out`` = [N][width], their evaluations on
+    the coset shift*<w_N> (``big_plan``'s size): ``small_plan.inverse_matrix`` followed by
+    ``big_plan.lde_matrix``.  The inverse overwrites ``evals`` with the coefficients."""
+    if big_plan.log_n < small_plan.log_n:
+        raise ValueError("big_plan must be at least as large as small_plan")
+    if (small_plan.p, small_plan.limbs64, small_plan.elem_bytes, small_plan.montgomery_io) != \
+            (big_plan.p, big_plan.limbs64, big_plan.elem_bytes, big_plan.montgomery_io):
+        raise ValueError("the two plans must share field, element layout and Montgomery-I/O mode")
+    big_plan._check_lde_matrix(evals, out, big_plan.log_n - small_plan.log_n, shift, width)
+    small_plan.inverse_matrix(evals, width, stream=stream)
+    return big_plan.lde_matrix(evals, out, big_plan.log_n - small_plan.log_n, shift, width, stream=stream)
 
 
 # ------------------------------------------------------------------------------------ shims
