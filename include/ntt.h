@@ -292,6 +292,34 @@ int ntt_lde_matrix(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_b
                    unsigned width, void* hip_stream);
 int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]);
 
+/* The matrix calls on a coset and with the evaluations' rows in bit-reversed order: the two steps around
+ * a prover's extension (quotient evaluations on c<w_n> back to coefficients; rows stored so that FRI's
+ * fold partners k and k + N/2 are adjacent and the first N / 2^k rows are a sub-coset).
+ *   ntt_forward_matrix_ex: in place, out[k][b] = sum_j in[j][b] (c w_n^k)^j -- the product by c^j rides at
+ *     the first pass's load, as in ntt_lde_matrix;
+ *   ntt_inverse_matrix_ex: in place, out[j][b] = c^-j INTT(column b)_j -- the product by c^-j rides at
+ *     the last pass's store;
+ *   ntt_lde_matrix_ex: ntt_lde_matrix with `order`.
+ * c = *shift, canonical and nonzero (one uint64_t on these engines; canonical on NTT_PLAN_MONTGOMERY_IO
+ * plans too), sharing ntt_lde_batch's cached tables; shift == NULL is c = 1: no product, and the shift
+ * cache is not touched.
+ * order: NTT_MATRIX_BITREV_OUT (forward, lde): row k of the natural result is stored at row
+ * bitrev(k); NTT_MATRIX_BITREV_IN (inverse): row i of d_data holds the evaluation of natural index
+ * bitrev(i).  bitrev reverses the plan's log_n bits (for an lde: of the large size N).  A row map picks
+ * another row for the same run of columns, so it costs no coalescing; neither option adds a launch, a pass
+ * or a buffer, and ntt_plan_matrix_info and the launch labels are those of the plain calls.
+ * With shift == NULL and order == 0 each call is its plain form: the same launches, the same bits.
+ * NTT_ERR_ARG before any launch, the buffers untouched: whatever the plain calls refuse, an unknown bit in
+ * `order`, NTT_MATRIX_BITREV_IN on forward or lde, NTT_MATRIX_BITREV_OUT on inverse, a bad shift. */
+#define NTT_MATRIX_BITREV_OUT 1u
+#define NTT_MATRIX_BITREV_IN 2u
+int ntt_forward_matrix_ex(ntt_plan* plan, void* d_data, unsigned width, const uint64_t* shift, unsigned order,
+                          void* hip_stream);
+int ntt_inverse_matrix_ex(ntt_plan* plan, void* d_data, unsigned width, const uint64_t* shift, unsigned order,
+                          void* hip_stream);
+int ntt_lde_matrix_ex(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
+                      unsigned width, unsigned order, void* hip_stream);
+
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */
 int ntt_pointwise_mul(ntt_plan* plan, const void* d_a, const void* d_b, void* d_c, void* hip_stream);

@@ -188,8 +188,15 @@ struct PassArgs {
   // strip g mod mat_ns of tile g / mat_ns (the strips of one tile share lines: they run together)
   uint32_t mat_w;   // columns of the matrix
   uint32_t mat_ns;  // strips per row: ceil(mat_w / 2^il)
+  uint32_t mat_ops; // MAT_* bits (ntt_*_matrix_ex): row maps of the first / last pass, the c^-j epilogue
 };
 enum : uint32_t { FS_MAP_IN = 1u, FS_MAP_OUT = 2u, FS_IL = 4u, FS_MAP_EPI = 8u };
+// PassArgs::mat_ops.  A row map changes which row a strip's run of columns belongs to, never the run:
+//   MAT_REV_IN   the pass that reads the caller's matrix loads natural row j from row bitrev_log_n(j);
+//   MAT_REV_OUT  the pass that writes the caller's matrix stores natural row k at row bitrev_log_n(k);
+//   MAT_MUL_OUT  that pass multiplies natural output row j by tw_in[j mod 2^lo_bits] tw_in_hi[j >> lo_bits]
+//                (the shift's inverse tables: c^-j) before the store; tw_in is then not a load-side table.
+enum : uint32_t { MAT_REV_IN = 1u, MAT_REV_OUT = 2u, MAT_MUL_OUT = 4u };
 
 // Fused single-launch schedule of a 3-pass transform (k_fused3, BASELINE config 2's "single-kernel"):
 // one persistent launch runs pass 1's, pass 2's and the final pass's tiles, handed between

@@ -552,11 +552,25 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
     if (single_il) pos = (pos << A.il) + b;
     return (A.fs & FS_MAP_EPI) ? A.mepi(pos, 0) : pos;
   };
-  // MAT: the address of interleaved index P of this strip; false: the column does not exist
-  auto mat_at = [&](size_t P, size_t& at) -> bool {
+  // MAT: the address of interleaved index P of this strip; false: the column does not exist.  rev (the
+  // load of the first pass, the store of the last: MAT_REV_IN / MAT_REV_OUT): the row is stored at its
+  // log_n-bit reversal -- another row, the same run of columns within it
+  auto mat_at = [&](size_t P, size_t& at, bool rev = false) -> bool {
     const uint32_t col = (bq << A.il) + (uint32_t)(P & ((1u << A.il) - 1));
-    at = (P >> A.il) * A.mat_w + col;
+    uint32_t row = (uint32_t)(P >> A.il);
+    if (rev) row = __builtin_bitreverse32(row) >> (32 - A.log_n);  // log_n >= 3 in a pass
+    at = (size_t)row * A.mat_w + col;
     return col < A.mat_w;
+  };
+  // MAT_MUL_OUT: natural output row j times c^-j, the two-level product of the load side (PRO_LDE)
+  auto mat_mul_out = [&]([[maybe_unused]] uint32_t (&v)[E::W], [[maybe_unused]] uint32_t row) {
+    if constexpr (MAT) {
+      typename E::Tw tl, th;
+      E::tload(tl, A.tw_in, row & ((1u << A.lo_bits) - 1));
+      E::tload(th, A.tw_in_hi, row >> A.lo_bits);
+      E::mul(tl.w, th, A.F);
+      E::mulv(v, tl.w, A.F);
+    }
   };
   // debug builds: an index outside its buffer is recorded and redirected to element 0
   auto ck = [&](size_t i, [[maybe_unused]] size_t lim) -> size_t {
@@ -690,7 +704,7 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
           }
         } else if constexpr (MAT) {
           size_t at;
-          if (mat_at(pos, at)) {
+          if (mat_at(pos, at, KIND == KIND_COLUMN && (A.mat_ops & MAT_REV_IN))) {
             E::template load<SW>(x[j * Q + d], src, ck(at, A.dbg_src_n));
 #if NTT_DEBUG_CHECKS
             if (KIND == KIND_COLUMN && A.src_user) {
@@ -827,8 +841,14 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
           }
           pos = colbase + c + ((size_t)kn << log_s);
           if constexpr (MAT) {  // scratch (or, for a transform of one pass, the caller's buffer) in the matrix's own layout
+            // a transform of one pass: its rows are the natural outputs (the c^-j epilogue, the row map)
             size_t at;
-            if (mat_at(pos, at)) E::template store_lazy<E::MUL_OUT, FAST, DW, WT>(dst, ck(at, A.dbg_dst_n), v, A.F);
+            if (mat_at(pos, at, (A.mat_ops & MAT_REV_OUT) != 0)) {
+              if constexpr (PRO == PRO_NONE) {
+                if (A.mat_ops & MAT_MUL_OUT) mat_mul_out(v, (uint32_t)(pos >> A.il));
+              }
+              E::template store_lazy<E::MUL_OUT, FAST, DW, WT>(dst, ck(at, A.dbg_dst_n), v, A.F);
+            }
           } else {
             E::template store_lazy<E::MUL_OUT, FAST, DW, WT>(dst, ck(pos, A.dbg_dst_n), v, A.F);  // scratch: < 2p, read by the next pass
           }
@@ -848,7 +868,14 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
             E::template store<E::MUL_OUT, FAST, DW>(dst, ck(out_pos(pos, bq), A.dbg_dst_n), v, A.F);
           } else if constexpr (MAT) {
             size_t at;
-            if (mat_at(pos, at)) E::template store<E::IN * Q, FAST, DW>(dst, ck(at, A.dbg_dst_n), v, A.F);
+            if (mat_at(pos, at, (A.mat_ops & MAT_REV_OUT) != 0)) {
+              if (A.mat_ops & MAT_MUL_OUT) {
+                mat_mul_out(v, (uint32_t)(pos >> A.il));
+                E::template store<E::MUL_OUT, FAST, DW>(dst, ck(at, A.dbg_dst_n), v, A.F);
+              } else {
+                E::template store<E::IN * Q, FAST, DW>(dst, ck(at, A.dbg_dst_n), v, A.F);
+              }
+            }
           } else {
             E::template store<E::IN * Q, FAST, DW>(dst, ck(out_pos(pos, bq), A.dbg_dst_n), v, A.F);
           }
@@ -2452,10 +2479,16 @@ static hipError_t launch_mat_r(int kind, bool lde, const uint32_t* src, uint32_t
     if (A.mat_w == 0 || A.mat_ns == 0 || A.il + LOGR > (uint32_t)E::TILE_LOG || A.fs || A.tw_epi || A.src2 ||
         A.tw_full || A.tw_sh)
       return hipErrorInvalidValue;
+    // the row maps reverse log_n bits of a 32-bit row; the epilogue needs both of its tables, and is the
+    // only use of tw_in outside the PRO_LDE pass
+    if (A.log_n < (uint32_t)LOGR || A.log_n > 31 || (A.mat_ops & ~(MAT_REV_IN | MAT_REV_OUT | MAT_MUL_OUT)))
+      return hipErrorInvalidValue;
+    const bool mul_out = (A.mat_ops & MAT_MUL_OUT) != 0;
+    if (mul_out && (lde || !A.tw_in || !A.tw_in_hi)) return hipErrorInvalidValue;
     if (kind == KIND_COLUMN && lde) {
-      if (A.src_stride == 0) return hipErrorInvalidValue;
+      if (A.src_stride == 0 || (A.mat_ops & MAT_REV_IN)) return hipErrorInvalidValue;
       hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_COLUMN, PRO_LDE>), g, b, 0, st, src, dst, A);
-    } else if (lde || A.tw_in) {
+    } else if (lde || (A.tw_in && !mul_out)) {
       return hipErrorInvalidValue;
     } else if (kind == KIND_COLUMN) {
       hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_COLUMN, PRO_NONE>), g, b, 0, st, src, dst, A);
@@ -2488,16 +2521,31 @@ hipError_t launch_mat_pass(int kind, int logr, bool lde, const uint32_t* src, ui
 template <class E>
 __global__ void k_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E> A, uint32_t n_in) {
   const uint32_t n = 1u << A.log_n;
+  const bool mul_out = (A.mat_ops & MAT_MUL_OUT) != 0;
+  // the row maps (MAT_REV_IN / MAT_REV_OUT): log_n is 1 or 2 here
+  auto row_of = [&](uint32_t r, uint32_t bit) -> uint32_t {
+    return (A.mat_ops & bit) ? __builtin_bitreverse32(r) >> (32 - A.log_n) : r;
+  };
+  // debug builds: an index outside its buffer is recorded and redirected to element 0
+  auto ck = [&](size_t i, [[maybe_unused]] size_t lim) -> size_t {
+#if NTT_DEBUG_CHECKS
+    if (i >= lim) {
+      ntt_dbg_flag(A.F.dbg, NTT_DBG_BOUNDS);
+      return 0;
+    }
+#endif
+    return i;
+  };
   NTT_GRID_STRIDE(b, A.mat_w) {
     uint32_t x[4][E::W];
     static_for<4>([&](auto J) {
       constexpr int j = J;
       if (j < n_in) {
-        E::load(x[j], src, (size_t)j * A.mat_w + b);
+        E::load(x[j], src, ck((size_t)row_of(j, MAT_REV_IN) * A.mat_w + b, A.dbg_src_n));
 #if NTT_DEBUG_CHECKS
         if (!E::dbg_canonical(x[j], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
 #endif
-        if (A.tw_in) {  // c^j from the shift's two-level tables
+        if (A.tw_in && !mul_out) {  // c^j from the shift's two-level tables
           typename E::Tw tl, th;
           E::tload(tl, A.tw_in, (uint32_t)(j & ((1u << A.lo_bits) - 1)));
           E::tload(th, A.tw_in_hi, (uint32_t)(j >> A.lo_bits));
@@ -2527,7 +2575,14 @@ __global__ void k_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E
           }
         });
         if (A.flags & 1u) E::mul(acc, A.F.ninv, A.F);
-        E::template store<E::IN>(dst, (size_t)k * A.mat_w + b, acc, A.F);
+        if (mul_out) {  // c^-k, the shift's inverse tables
+          typename E::Tw tl, th;
+          E::tload(tl, A.tw_in, (uint32_t)(k & ((1u << A.lo_bits) - 1)));
+          E::tload(th, A.tw_in_hi, (uint32_t)(k >> A.lo_bits));
+          E::mul(tl.w, th, A.F);
+          E::mulv(acc, tl.w, A.F);
+        }
+        E::template store<E::IN>(dst, ck((size_t)row_of(k, MAT_REV_OUT) * A.mat_w + b, A.dbg_dst_n), acc, A.F);
       }
     });
   }

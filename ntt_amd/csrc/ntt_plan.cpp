@@ -91,8 +91,9 @@ struct PlanBase {
                   unsigned batch, hipStream_t st) = 0;
   // the columns of a row-major [n][width] matrix (ntt_forward_matrix / ntt_inverse_matrix: in == out;
   // ntt_lde_matrix: is_lde, in = [n >> log_blowup][width]) and the schedule those calls run
+  // order: NTT_MATRIX_BITREV_* (the _ex calls); shift: the lde's and the _ex calls' coset, null: c = 1
   virtual int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
-                     const uint64_t* shift, unsigned limbs64, hipStream_t st) = 0;
+                     const uint64_t* shift, unsigned limbs64, unsigned order, hipStream_t st) = 0;
   virtual int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
@@ -744,22 +745,28 @@ struct PlanImpl final : PlanBase {
     }
   }
   // in: [n_in = n >> log_blowup][width] (is_lde) or the matrix itself (in == out); out: [n][width]
+  // The _ex forms change addresses and one product, never the schedule: a forward shift is the lde's
+  // product at the first pass's load (PRO_LDE with every row present: it loads what the plain pass loads,
+  // all of it ahead of the tile's first store, so a transform of one pass stays safe in place); an inverse
+  // shift is c^-j at the last pass's store; BITREV_IN permutes the rows the first pass loads, BITREV_OUT
+  // the rows the last pass stores.
   int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
-             const uint64_t* shift, unsigned limbs64, hipStream_t st) override {
+             const uint64_t* shift, unsigned limbs64, unsigned order, hipStream_t st) override {
     if constexpr (!HasMat<E>::value) {
       return NTT_ERR_ARG;
     } else {
       if (!in || !out || width == 0 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
       if (((uint64_t)n * width) >> 32) return NTT_ERR_ARG;  // element indices are 32-bit in places
       if (is_lde && log_blowup > log_n) return NTT_ERR_ARG;
+      if (order & ~(inverse ? NTT_MATRIX_BITREV_IN : NTT_MATRIX_BITREV_OUT)) return NTT_ERR_ARG;
       const size_t n_in = is_lde ? (size_t)(n >> log_blowup) : (size_t)n, eb = (size_t)MEMW * 4;
       if (is_lde) {
         const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * width * eb;
         const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)n * width * eb;
         if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // the first pass reads d_in while later tiles write d_out
-        if (shift)
-          if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
       }
+      if (shift)
+        if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
       unsigned tb[8] = {0}, rr[8], p = 0;
       if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), width, rr, tb, p)) return NTT_ERR_ARG;
       if (!mat_state.ready([&] { return build_mat(); })) return NTT_ERR_HIP;
@@ -770,7 +777,11 @@ struct PlanImpl final : PlanBase {
         return NTT_OK;
       }
       const int dir = inverse ? 1 : 0;
-      const bool shifted = is_lde && shift;
+      // forward: c^j at the first pass's load (the lde's pass, here maybe with n_in = n and in == out);
+      // inverse: c^-j at the last pass's store
+      const bool mul_in = !inverse && shift, mul_out = inverse && shift;
+      const bool pro_lde = is_lde || mul_in;
+      const unsigned last = mat_p == 0 ? 0 : mat_p - 1;
       auto mat_args = [&](unsigned i) {
         PassArgs<E> A = base_args(inverse);
         A.tw_int = d_mat_tab.get() + mat_int[dir][i];
@@ -778,13 +789,20 @@ struct PlanImpl final : PlanBase {
         A.il = tb[i];
         A.mat_ns = (uint32_t)(((uint64_t)width + (1u << tb[i]) - 1) >> tb[i]);
         A.dbg_src_n = A.dbg_dst_n = (size_t)n * width;
-        if (i == 0 && is_lde) {
+        if (i == 0 && pro_lde) {
           A.src_stride = n_in * MEMW;
           A.dbg_src_n = n_in * width;
-          if (shifted) {
+          if (mul_in) {
             A.tw_in = d_coset.get() + coset_off[0][0];
             A.tw_in_hi = d_coset.get() + coset_off[0][1];
           }
+        }
+        if (i == 0 && (order & NTT_MATRIX_BITREV_IN)) A.mat_ops |= MAT_REV_IN;
+        if (i == last && (order & NTT_MATRIX_BITREV_OUT)) A.mat_ops |= MAT_REV_OUT;
+        if (i == last && mul_out) {
+          A.mat_ops |= MAT_MUL_OUT;
+          A.tw_in = d_coset.get() + coset_off[1][0];
+          A.tw_in_hi = d_coset.get() + coset_off[1][1];
         }
         return A;
       };
@@ -812,7 +830,7 @@ struct PlanImpl final : PlanBase {
         A.log_m = log_n - blk;
         A.src_user = i == 0 ? 1u : 0u;
         const uint32_t grid = (uint32_t)(((n << tb[i]) >> E::TILE_LOG) * A.mat_ns);
-        e = launch_mat_pass<E>(KIND_COLUMN, (int)mat_r[i], i == 0 && is_lde, i == 0 ? src : work, work, A, grid, st);
+        e = launch_mat_pass<E>(KIND_COLUMN, (int)mat_r[i], i == 0 && pro_lde, i == 0 ? src : work, work, A, grid, st);
         mark(st, mat_p == 1 ? "s" : "c", mat_r[i]);
         blk -= mat_r[i];
       }
@@ -1783,21 +1801,32 @@ int ntt_lde_batch(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_bl
 
 // Row-major matrix transforms: the plan's own engine on the matrix schedule (never the second plan)
 static int run_matrix(ntt_plan* plan, const void* in, void* out, unsigned width, bool inverse, bool is_lde,
-                      unsigned log_blowup, const uint64_t* shift, void* s) {
+                      unsigned log_blowup, const uint64_t* shift, unsigned order, void* s) {
   return on_device(plan, [&](PlanBase& P) {
     plan->last = &P;
-    return P.matrix(in, out, width, inverse, is_lde, log_blowup, shift, 1, S(s));
+    return P.matrix(in, out, width, inverse, is_lde, log_blowup, shift, 1, order, S(s));
   });
 }
 int ntt_forward_matrix(ntt_plan* plan, void* d, unsigned width, void* s) {
-  return run_matrix(plan, d, d, width, false, false, 0, nullptr, s);
+  return run_matrix(plan, d, d, width, false, false, 0, nullptr, 0, s);
 }
 int ntt_inverse_matrix(ntt_plan* plan, void* d, unsigned width, void* s) {
-  return run_matrix(plan, d, d, width, true, false, 0, nullptr, s);
+  return run_matrix(plan, d, d, width, true, false, 0, nullptr, 0, s);
 }
 int ntt_lde_matrix(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
                    unsigned width, void* s) {
-  return run_matrix(plan, d_in, d_out, width, false, true, log_blowup, shift, s);
+  return run_matrix(plan, d_in, d_out, width, false, true, log_blowup, shift, 0, s);
+}
+// ... on a coset and / or with the rows of the evaluations in bit-reversed order
+int ntt_forward_matrix_ex(ntt_plan* plan, void* d, unsigned width, const uint64_t* shift, unsigned order, void* s) {
+  return run_matrix(plan, d, d, width, false, false, 0, shift, order, s);
+}
+int ntt_inverse_matrix_ex(ntt_plan* plan, void* d, unsigned width, const uint64_t* shift, unsigned order, void* s) {
+  return run_matrix(plan, d, d, width, true, false, 0, shift, order, s);
+}
+int ntt_lde_matrix_ex(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
+                      unsigned width, unsigned order, void* s) {
+  return run_matrix(plan, d_in, d_out, width, false, true, log_blowup, shift, order, s);
 }
 int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;

@@ -35,6 +35,8 @@ NTT_PLAN_IMPROVED_V2 = 1024
 NTT_PLAN_IMPROVED_V3 = 2048
 NTT_PLAN_IMPROVED_V4 = 4096
 NTT_PLAN_ELEM32 = 8192
+NTT_MATRIX_BITREV_OUT = 1
+NTT_MATRIX_BITREV_IN = 2
 
 # Every symbol declared in include/ntt.h with its ctypes prototype: (restype, argtypes).
 _vp = C.c_void_p
@@ -54,6 +56,9 @@ PROTOTYPES = {
     "ntt_inverse_matrix": (C.c_int, [_vp, _vp, C.c_uint, _vp]),
     "ntt_lde_matrix": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
     "ntt_plan_matrix_info": (C.c_int, [_vp, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "ntt_forward_matrix_ex": (C.c_int, [_vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
+    "ntt_inverse_matrix_ex": (C.c_int, [_vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
+    "ntt_lde_matrix_ex": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, C.c_uint, _vp]),
     "ntt_polymul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ntt_fill": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _vp]),
     "ntt_plan_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_uint),

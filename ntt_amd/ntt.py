@@ -295,21 +295,48 @@ class NTTPlan:
         if t.device.index != self.device:
             raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
 
-    def forward_matrix(self, t: torch.Tensor, width: int, stream=None) -> torch.Tensor:
+    def _check_matrix_ex(self, shift, flag, flag_name: str) -> None:
+        """The keyword options of the matrix calls: a canonical nonzero integer shift (or None), a bool flag."""
+        if shift is not None and (not isinstance(shift, int) or isinstance(shift, bool) or not 0 < shift < self.p):
+            raise ValueError(f"shift must be None or a canonical nonzero integer (0 < shift < p), not {shift!r}")
+        if not isinstance(flag, bool):
+            raise ValueError(f"{flag_name} must be a bool, not {flag!r}")
+
+    def forward_matrix(self, t: torch.Tensor, width: int, stream=None, *, shift: Optional[int] = None,
+                       bitrev_out: bool = False) -> torch.Tensor:
         """Forward NTT of every column of the row-major matrix ``t`` = [n][width] in place
-        (ntt_forward_matrix): element (j, b) at ``t.view(-1)[j * width + b]``."""
+        (ntt_forward_matrix): element (j, b) at ``t.view(-1)[j * width + b]``.  ``shift`` = c evaluates on
+        the coset c<w_n> instead: out[k][b] = sum_j t[j][b] (c w_n^k)^j; ``bitrev_out`` stores row k of the
+        result at row bitrev(k) (ntt_forward_matrix_ex)."""
+        self._check_matrix_ex(shift, bitrev_out, "bitrev_out")
         self._check_matrix(t, self.n, width, "t")
         self._check_matrix_device(t, "t")
-        _L.check(self._lib.ntt_forward_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
-                                              _stream_ptr(stream, t.device)), "ntt_forward_matrix")
+        if shift is None and not bitrev_out:
+            _L.check(self._lib.ntt_forward_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
+                                                  _stream_ptr(stream, t.device)), "ntt_forward_matrix")
+            return t
+        sh = None if shift is None else _u64_array(int_to_limbs(shift, self.limbs64))
+        _L.check(self._lib.ntt_forward_matrix_ex(self._h, C.c_void_p(t.data_ptr()), int(width), sh,
+                                                 _L.NTT_MATRIX_BITREV_OUT if bitrev_out else 0,
+                                                 _stream_ptr(stream, t.device)), "ntt_forward_matrix_ex")
         return t
 
-    def inverse_matrix(self, t: torch.Tensor, width: int, stream=None) -> torch.Tensor:
-        """Inverse NTT (1/n included) of every column of the row-major matrix ``t`` = [n][width] in place."""
+    def inverse_matrix(self, t: torch.Tensor, width: int, stream=None, *, shift: Optional[int] = None,
+                       bitrev_in: bool = False) -> torch.Tensor:
+        """Inverse NTT (1/n included) of every column of the row-major matrix ``t`` = [n][width] in place.
+        ``shift`` = c interpolates from the coset c<w_n>: out[j][b] = c^-j INTT(column b)_j; ``bitrev_in``:
+        row i of ``t`` holds the evaluation of natural index bitrev(i) (ntt_inverse_matrix_ex)."""
+        self._check_matrix_ex(shift, bitrev_in, "bitrev_in")
         self._check_matrix(t, self.n, width, "t")
         self._check_matrix_device(t, "t")
-        _L.check(self._lib.ntt_inverse_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
-                                              _stream_ptr(stream, t.device)), "ntt_inverse_matrix")
+        if shift is None and not bitrev_in:
+            _L.check(self._lib.ntt_inverse_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
+                                                  _stream_ptr(stream, t.device)), "ntt_inverse_matrix")
+            return t
+        sh = None if shift is None else _u64_array(int_to_limbs(shift, self.limbs64))
+        _L.check(self._lib.ntt_inverse_matrix_ex(self._h, C.c_void_p(t.data_ptr()), int(width), sh,
+                                                 _L.NTT_MATRIX_BITREV_IN if bitrev_in else 0,
+                                                 _stream_ptr(stream, t.device)), "ntt_inverse_matrix_ex")
         return t
 
     def _check_lde_matrix(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int],
@@ -328,13 +355,21 @@ class NTTPlan:
         self._check_matrix_device(out, "out")
 
     def lde_matrix(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int] = None,
-                   width: int = 1, stream=None) -> torch.Tensor:
+                   width: int = 1, stream=None, *, bitrev_out: bool = False) -> torch.Tensor:
         """Low-degree extension of the columns of a row-major matrix (ntt_lde_matrix).  This plan has the
         LARGE size N = 2^log_n; ``coeffs`` = [N >> log_blowup][width] holds one polynomial per column,
         ``out`` = [N][width] receives out[k][b] = sum_j coeffs[j][b] (shift w_N^k)^j (shift None: 1).
-        ``coeffs`` is not modified and must not overlap ``out``."""
+        ``coeffs`` is not modified and must not overlap ``out``.  ``bitrev_out`` stores row k of the result
+        at row bitrev(k), the reversal over this plan's log_n bits (ntt_lde_matrix_ex)."""
+        if not isinstance(bitrev_out, bool):
+            raise ValueError(f"bitrev_out must be a bool, not {bitrev_out!r}")
         self._check_lde_matrix(coeffs, out, log_blowup, shift, width)
         sh = None if shift is None else _u64_array(int_to_limbs(int(shift), self.limbs64))
+        if bitrev_out:
+            _L.check(self._lib.ntt_lde_matrix_ex(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                 int(log_blowup), sh, int(width), _L.NTT_MATRIX_BITREV_OUT,
+                                                 _stream_ptr(stream, out.device)), "ntt_lde_matrix_ex")
+            return out
         _L.check(self._lib.ntt_lde_matrix(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
                                           int(log_blowup), sh, int(width), _stream_ptr(stream, out.device)),
                  "ntt_lde_matrix")
@@ -464,19 +499,24 @@ def lde_from_evals(small_plan: NTTPlan, big_plan: NTTPlan, evals: torch.Tensor, 
 
 
 def lde_matrix_from_evals(small_plan: NTTPlan, big_plan: NTTPlan, evals: torch.Tensor, out: torch.Tensor,
-                          shift: Optional[int] = None, width: int = 1, stream=None) -> torch.Tensor:
+                          shift: Optional[int] = None, width: int = 1, stream=None, *,
+                          in_shift: Optional[int] = None, bitrev_out: bool = False) -> torch.Tensor:
     """The matrix form of ``lde_from_evals``: ``evals`` = [n][width] row-major, the evaluations of one
     polynomial per column on <w_n> (``small_plan``'s size) -> ``out`` = [N][width], their evaluations on
     the coset shift*<w_N> (``big_plan``'s size): ``small_plan.inverse_matrix`` followed by
-    ``big_plan.lde_matrix``.  The inverse overwrites ``evals`` with the coefficients."""
+    ``big_plan.lde_matrix``.  The inverse overwrites ``evals`` with the coefficients.  ``in_shift``: the
+    evaluations are given on the coset in_shift*<w_n> and interpolated with the coset inverse;
+    ``bitrev_out``: ``out`` gets its rows in bit-reversed order (over ``big_plan``'s log_n bits)."""
     if big_plan.log_n < small_plan.log_n:
         raise ValueError("big_plan must be at least as large as small_plan")
     if (small_plan.p, small_plan.limbs64, small_plan.elem_bytes, small_plan.montgomery_io) != \
             (big_plan.p, big_plan.limbs64, big_plan.elem_bytes, big_plan.montgomery_io):
         raise ValueError("the two plans must share field, element layout and Montgomery-I/O mode")
+    small_plan._check_matrix_ex(in_shift, bitrev_out, "bitrev_out")
     big_plan._check_lde_matrix(evals, out, big_plan.log_n - small_plan.log_n, shift, width)
-    small_plan.inverse_matrix(evals, width, stream=stream)
-    return big_plan.lde_matrix(evals, out, big_plan.log_n - small_plan.log_n, shift, width, stream=stream)
+    small_plan.inverse_matrix(evals, width, stream=stream, shift=in_shift)
+    return big_plan.lde_matrix(evals, out, big_plan.log_n - small_plan.log_n, shift, width, stream=stream,
+                               bitrev_out=bitrev_out)
 
 
 # ------------------------------------------------------------------------------------ shims

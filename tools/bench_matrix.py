@@ -17,6 +17,13 @@ compared bit for bit.  `matrix_gbs` is the bytes the matrix call must move (each
 the matrix once; an extension's first pass reads the n coefficient rows only) over its time, and
 `matrix_hbm_frac` that rate over the 6.3 TB/s a streaming copy reaches on this device (8 TB/s spec).
 
+After the two plain rows of a case comes one `variants` row: the coset forward, the bit-reversed forward,
+the coset inverse and the bit-reversed extension (forward_matrix(shift=g), forward_matrix(bitrev_out=True),
+inverse_matrix(shift=g), lde_matrix(bitrev_out=True)), each timed interleaved with the plain call of the
+same shape in the same loop; `<variant>_over_plain` is the variant's median over the plain call's (1.0 =
+free), and the per-launch times of the plain and the coset inverse show what the c^-j epilogue costs the
+final pass.  --no-variants leaves that row out (a library without the _ex calls).
+
 Every case runs as a child process under its own `timeout -k 10`; the driver stops at the first that fails.
 
     python tools/bench_matrix.py [--out profiles/matrix/bench.jsonl]
@@ -36,7 +43,56 @@ CASES = [("babybear", 4, 16), ("babybear", 4, 37), ("babybear", 4, 256), ("goldi
 HBM_COPY_TBS = 6.3
 
 
-def child(name, fid, width, steps, warmup):
+def variants(pl, name, width, g, x_rows, steps, warmup):
+    import torch
+    N, n_in = pl.n, pl.n >> 1
+    src = x_rows[:n_in].contiguous().view(-1)
+    data = x_rows.contiguous().view(-1).clone()  # transformed in place over and over: the time does not depend on the values
+    out = torch.empty(N * width, dtype=pl.dtype, device="cuda:0")
+    routes = {
+        "forward": lambda: pl.forward_matrix(data, width),
+        "forward_coset": lambda: pl.forward_matrix(data, width, shift=g),
+        "forward_bitrev": lambda: pl.forward_matrix(data, width, bitrev_out=True),
+        "inverse": lambda: pl.inverse_matrix(data, width),
+        "inverse_coset": lambda: pl.inverse_matrix(data, width, shift=g),
+        "lde": lambda: pl.lde_matrix(src, out, 1, g, width),
+        "lde_bitrev": lambda: pl.lde_matrix(src, out, 1, g, width, bitrev_out=True),
+    }
+    plain_of = {"forward_coset": "forward", "forward_bitrev": "forward", "inverse_coset": "inverse", "lde_bitrev": "lde"}
+    for _ in range(warmup):
+        for f in routes.values():
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in routes}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(steps):
+        for k, f in routes.items():
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    launches = {}
+    pl.set_profiling(True)
+    for k, f in routes.items():
+        f()
+        torch.cuda.synchronize()
+        launches[k] = dict(zip(pl.last_launch_labels(), [round(v, 4) for v in pl.last_launch_ms()]))
+    pl.set_profiling(False)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    row = {"field": name, "log_n": LOG_N, "width": width, "op": "variants", "matrix_passes": pl.matrix_passes(width),
+           "steps": steps, "warmup": warmup}
+    for k in routes:
+        row[k + "_ms"] = round(med[k], 5)
+        row[k + "_min_ms"] = round(min(ms[k]), 5)
+        row[k + "_max_ms"] = round(max(ms[k]), 5)
+    for k, plain in plain_of.items():
+        row[k + "_over_plain"] = round(med[k] / med[plain], 3)
+    row["launch_ms"] = launches
+    print("ROW " + json.dumps(row), flush=True)
+
+
+def child(name, fid, width, steps, warmup, with_variants=True):
     import torch
 
     from ntt_amd.fields import field_params
@@ -124,6 +180,8 @@ def child(name, fid, width, steps, warmup):
                "matrix_hbm_frac": round(gbs / (HBM_COPY_TBS * 1e3), 3),
                "matrix_launch_ms": launches, "batched_launch_ms": launches_b}
         print("ROW " + json.dumps(row), flush=True)
+    if with_variants:
+        variants(pl, name, width, g, x_rows, steps, warmup)
 
 
 def main():
@@ -131,18 +189,19 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "matrix", "bench.jsonl"))
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-variants", action="store_true", help="only the plain rows (a library without the _ex calls)")
     ap.add_argument("--child", nargs=3, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.steps < 20:
         raise SystemExit("--steps: the median is taken over at least 20 steps")
     if a.child:
         name, fid, width = a.child
-        child(name, int(fid), int(width), a.steps, a.warmup)
+        child(name, int(fid), int(width), a.steps, a.warmup, not a.no_variants)
         return
     rows = []
     for name, fid, width in CASES:
         cmd = ["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--child", name, str(fid), str(width)]
+               "--warmup", str(a.warmup), "--child", name, str(fid), str(width)] + (["--no-variants"] if a.no_variants else [])
         r = subprocess.run(cmd, capture_output=True, text=True)
         for line in r.stdout.splitlines():
             if line.startswith("ROW "):
