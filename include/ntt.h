@@ -320,6 +320,40 @@ int ntt_inverse_matrix_ex(ntt_plan* plan, void* d_data, unsigned width, const ui
 int ntt_lde_matrix_ex(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
                       unsigned width, unsigned order, void* hip_stream);
 
+/* FRI fold of bit-reversed coset evaluations: the step after ntt_lde_matrix_ex(..., width = d,
+ * NTT_MATRIX_BITREV_OUT), which consumes the order that call stores.  An extension element is ext_degree = d
+ * adjacent base-field coefficients, an element of the ring F_p[X]/(X^d - W), W = ext_w (the library does the
+ * ring arithmetic and does not test irreducibility); d = 1 is the base field.
+ * With L = log_rows, N = 2^L, k = log_arity, M = N >> k, c = *shift (1 when shift == NULL), w_N the plan's
+ * root g^((p-1)/N) and rev_b the reversal of b bits:
+ *   d_in  [N][d]: row i holds f(c w_N^rev_L(i)) for a polynomial f of degree < N with extension coefficients;
+ *   d_out [M][d]: with f(x) = sum_{t < 2^k} x^t f_t(x^(2^k)) and g(y) = sum_t beta^t f_t(y), row i' holds
+ *                 g(c^(2^k) w_M^rev_{L-k}(i')): the same convention one level down, on the coset
+ *                 c^(2^k) <w_M>, so folds chain with c^(2^k) as the next shift.
+ * In the evaluation domain: rows i' 2^k + j (j < 2^k) are the fibre over row i', at the points
+ * x0 zeta^rev_k(j), x0 = c w_N^rev_{L-k}(i'), zeta = w_N^M; u_t = 2^-k sum_j zeta^(-t rev_k(j)) in[i' 2^k + j]
+ * and out[i'] = sum_t (beta / x0)^t u_t -- for k = 1 the usual (lo + hi) / 2 + beta (lo - hi) / (2 x0).
+ * One fold of arity 2^k by beta equals k folds of arity 2 by beta, beta^2, beta^4, ... with shifts c, c^2,
+ * c^4, ..., bit for bit.
+ * log_rows is any value from log_arity up to the plan's log_n (one plan of the largest layer serves every
+ * later one); 1 <= log_arity <= 4; ext_degree 1, 2 or 4; ext_w canonical and nonzero when ext_degree > 1,
+ * ignored at 1; beta: ext_degree host words, each canonical; shift: one canonical nonzero host word or NULL,
+ * as ntt_forward_matrix_ex takes it -- but nothing is cached: the shift tables of the other calls are not
+ * touched (c^-1 is one host inversion per call).  beta, ext_w and shift are canonical on
+ * NTT_PLAN_MONTGOMERY_IO plans too; the data keep the plan's form: every product is by a constant or by a
+ * per-row scalar t held as t R, and mulv(x, t R) = x t in whichever form x is, so one code path serves both
+ * plan kinds and the outputs carry the inputs' form.
+ * Asynchronous on hip_stream; one launch; d_in is not modified; outputs are canonical.
+ * Engines: as the matrix calls (Goldilocks, BabyBear, KoalaBear, NTT_PLAN_ELEM32 custom plans); plans of
+ * fields 0-2 and of custom 4- and 6-limb moduli return NTT_ERR_ARG.
+ * NTT_ERR_ARG before any launch, the buffers untouched: a null plan or pointer, log_arity 0, above 4 or above
+ * log_rows, log_rows above the plan's log_n, ext_degree outside {1, 2, 4}, ext_w 0 or >= p when
+ * ext_degree > 1, a beta word >= p, a bad shift, overlapping byte ranges of d_in (N d elements) and d_out
+ * (M d elements), NTT_PLAN_TWIDDLE_ONLY plans. */
+int ntt_fri_fold(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_rows, unsigned log_arity,
+                 unsigned ext_degree, uint64_t ext_w, const uint64_t* beta, const uint64_t* shift,
+                 void* hip_stream);
+
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */
 int ntt_pointwise_mul(ntt_plan* plan, const void* d_a, const void* d_b, void* d_c, void* hip_stream);
@@ -379,7 +413,8 @@ int ntt_plan_last_launch_ms(ntt_plan* plan, float* ms, unsigned max_launches, un
 /* The same launches' labels, comma-separated, in launch order: a kind letter and the pass's log2
  * radix (c column pass, "s" appended when it reads a Shoup-pair outer table; f final pass; s one
  * transform per workgroup; r several per workgroup; i in-place final pass with the digit reversal;
- * d digit-reversal swap; b single launch; n naive), "" when unlabelled.  NTT_ERR_ARG when `cap`
+ * d digit-reversal swap; b single launch; n naive; x FRI fold, with log_arity for the radix), "" when
+ * unlabelled.  NTT_ERR_ARG when `cap`
  * bytes do not hold them.  New (round 6): benchmarks pair per-launch PMC bytes with launches by
  * label, not by position. */
 int ntt_plan_last_launch_labels(ntt_plan* plan, char* buf, unsigned cap);

@@ -44,6 +44,7 @@ SOURCES += [f"ntt_e256t_{k}.hip" for k in ("col", "single", "fin", "misc")]  # 4
 SOURCES += [f"ntt_eg_{k}.hip" for k in ("col", "single", "fin", "misc", "rows")]  # Goldilocks, 8-B elements (Eng64G)
 SOURCES += [f"ntt_e31_{k}.hip" for k in ("col", "single", "fin", "misc", "rows")]  # primes < 2^31, 4-B elements (Eng31)
 SOURCES += ["ntt_eg_mat.hip", "ntt_e31_mat.hip"]  # row-major matrix passes, the strip form (ntt_*_matrix)
+SOURCES += ["ntt_eg_fold.hip", "ntt_e31_fold.hip"]  # FRI fold of bit-reversed coset evaluations (ntt_fri_fold)
 SOURCES += ["ntt_plan.cpp", "ntt_rplan.cpp", "ntt_multi.cpp"]
 ARCH = os.environ.get("NTT_OFFLOAD_ARCH", "gfx950")
 

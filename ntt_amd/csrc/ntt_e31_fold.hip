@@ -1,0 +1,5 @@
+// Eng31 (primes < 2^31, 4-B elements): k_fri_fold instantiations, the FRI fold of bit-reversed coset evaluations (ntt_fri_fold).
+#include "ntt_fold_impl.hpp"
+namespace ntt {
+NTT_INSTANTIATE_FOLD(Eng31)
+}  // namespace ntt

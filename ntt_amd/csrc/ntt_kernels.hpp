@@ -326,6 +326,32 @@ hipError_t launch_mat_pass(int kind, int logr, bool lde, const uint32_t* src, ui
 template <class E>
 hipError_t launch_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t n_in, hipStream_t st);
 
+// ---- FRI fold of bit-reversed coset evaluations (ntt_fri_fold; k_fri_fold in ntt_fold_impl.hpp, instances
+// in ntt_eg_fold.hip and ntt_e31_fold.hip: the HasMat engines).  Every constant of a call is wave-uniform
+// and travels in the kernel arguments as a twiddle (E::Tw: a Shoup pair on Eng31, the value on Eng64G).
+template <class E>
+struct FoldArgs {
+  typename E::Args F;   // p, p^-1, the checked build's status word
+  const uint32_t* lo_s; // w_n^-e two-level tables of the plan: lo scaled by R_e, and
+  const uint32_t* hi;   // the plain hi table (no n^-1)
+  uint32_t lo_bits;
+  uint32_t tab_shift;   // log_n - log_rows: w_N^-e = w_n^-(e << tab_shift)
+  uint32_t log_m;       // log_rows - log_arity: the output has 2^log_m rows
+  uint32_t vec;         // d_in and d_out are 16-byte aligned: vector loads and stores
+  size_t src_words;     // 32-bit words of d_in (N d E::MEMW) and
+  size_t dst_words;     // of d_out (M d E::MEMW)
+  typename E::Tw cinv;      // c^-1
+  typename E::Tw scale;     // 2^-log_arity
+  typename E::Tw zeta[8];   // zeta^-e, zeta = w_N^M of order 2^log_arity, e < 2^(log_arity - 1)
+  typename E::Tw beta[4][4];   // [s][j]: coefficient j of beta^(2^s), and
+  typename E::Tw wbeta[4][4];  // of W beta^(2^s) (j >= 1)
+};
+// One launch: log_arity 1..4, ext_degree 1, 2 or 4; staged: the fibres reach their threads through LDS
+// (16 B per lane at consecutive addresses; needs A.vec), else each thread loads its own fibre.
+template <class E>
+hipError_t launch_fri_fold(unsigned log_arity, unsigned ext_degree, bool staged, const uint32_t* in, uint32_t* out,
+                           const FoldArgs<E>& A, hipStream_t st);
+
 template <class E>
 hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,
                            const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F,

@@ -95,6 +95,9 @@ struct PlanBase {
   virtual int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
                      const uint64_t* shift, unsigned limbs64, unsigned order, hipStream_t st) = 0;
   virtual int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const = 0;
+  // FRI fold of bit-reversed coset evaluations (ntt_fri_fold): [2^log_rows][d] -> [2^(log_rows - log_arity)][d]
+  virtual int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree,
+                   uint64_t ext_w, const uint64_t* beta, const uint64_t* shift, hipStream_t st) = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -853,6 +856,105 @@ struct PlanImpl final : PlanBase {
       return rc_of(e);
     }
   }
+
+  // ---- FRI fold (ntt_fri_fold): one launch of k_fri_fold.  Every constant is computed here, on the host,
+  // per call -- c^-1 (one inversion), 2^-k, the 2^(k-1) twiddles zeta^-e, and beta^(2^s), W beta^(2^s) for
+  // the k stages -- and travels in the kernel arguments; x0^-1's variable part w_N^-rev(i') comes from the
+  // plan's own inverse two-level tables (lo scaled by R_e, the plain hi: not the one carrying n^-1) at
+  // stride 2^(log_n - log_rows).  Nothing is cached, so the coset tables of the other calls stay as they are.
+  // The data keep their form: with t R_e as the variable operand mulv(x, t R_e) = x t whatever form x has,
+  // and the other products are by constants, so a NTT_PLAN_MONTGOMERY_IO plan runs the same code.
+  int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree, uint64_t ext_w,
+           const uint64_t* beta, const uint64_t* shift, hipStream_t st) override {
+    if constexpr (!HasMat<E>::value) {
+      return NTT_ERR_ARG;
+    } else {
+      if (!in || !out || !beta || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
+      if (log_arity < 1 || log_arity > 4 || log_arity > log_rows || log_rows > log_n) return NTT_ERR_ARG;
+      if (ext_degree != 1 && ext_degree != 2 && ext_degree != 4) return NTT_ERR_ARG;
+      const unsigned d = ext_degree, k = log_arity;
+      Vec<NH> pv;
+      for (int i = 0; i < NH; ++i) pv[i] = H.M.p[i];
+      // one host word -> a canonical element (false: not below p)
+      auto canon = [&](uint64_t v, Vec<NH>& o) {
+        o = Vec<NH>{};
+        o[0] = (uint32_t)v;
+        if constexpr (NH > 1) o[1] = (uint32_t)(v >> 32);
+        else if (v >> 32) return false;
+        return vec_lt<NH>(o, pv);
+      };
+      Vec<NH> wc{}, cc{}, bc[4];
+      if (d > 1 && (!canon(ext_w, wc) || wc == Vec<NH>{})) return NTT_ERR_ARG;
+      for (unsigned j = 0; j < d; ++j)
+        if (!canon(beta[j], bc[j])) return NTT_ERR_ARG;
+      if (shift && (!canon(*shift, cc) || cc == Vec<NH>{})) return NTT_ERR_ARG;
+      const size_t eb = (size_t)MEMW * 4, n_in = (size_t)1 << log_rows, n_out = n_in >> k;
+      {
+        const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * d * eb;
+        const uintptr_t b0 = (uintptr_t)out, b1 = b0 + n_out * d * eb;
+        if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // other workgroups still read d_in
+      }
+      FoldArgs<E> A{};
+      A.F = Ff;
+      A.lo_s = d_tab.get() + off_los_i;
+      A.hi = d_tab.get() + off_hi_i;
+      A.lo_bits = lo_bits;
+      A.tab_shift = log_n - log_rows;
+      A.log_m = log_rows - k;
+      A.vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+      A.src_words = n_in * d * MEMW;
+      A.dst_words = n_out * d * MEMW;
+      auto tw = [&](const Vec<NH>& m, typename E::Tw& t) {  // Montgomery-form host value -> twiddle
+        uint32_t enc[TW];
+        EH.encode(H.from_mont(m), enc);
+        static_assert(sizeof(typename E::Tw) == TW * 4, "a twiddle is its table entry");
+        memcpy(&t, enc, sizeof t);
+      };
+      tw(shift ? H.pow(H.to_mont(cc), pm2_) : H.r1, A.cinv);
+      {
+        Vec<NH> two{};
+        two[0] = 2;
+        tw(H.pow_u64(H.pow(H.to_mont(two), pm2_), k), A.scale);
+      }
+      {
+        const Vec<NH> zi = H.pow_u64(wn_m[1], n >> k);  // zeta^-1 = w_n^-(n / 2^k)
+        Vec<NH> acc = H.r1;
+        for (unsigned e = 0; e < 8; ++e) {
+          tw(acc, A.zeta[e]);
+          acc = H.mul(acc, zi);
+        }
+      }
+      {
+        const Vec<NH> wm = d > 1 ? H.to_mont(wc) : H.r1;
+        Vec<NH> b[4] = {}, zero{};
+        for (unsigned j = 0; j < d; ++j) b[j] = H.to_mont(bc[j]);
+        for (unsigned s = 0; s < 4; ++s) {
+          for (unsigned j = 0; j < 4; ++j) {
+            tw(j < d ? b[j] : zero, A.beta[s][j]);
+            tw(j < d ? H.mul(b[j], wm) : zero, A.wbeta[s][j]);
+          }
+          // b <- b^2 in F_p[X]/(X^d - W)
+          Vec<NH> lo[4] = {}, hi[4] = {};
+          for (unsigned i = 0; i < d; ++i)
+            for (unsigned j = 0; j < d; ++j) {
+              Vec<NH>& acc = i + j < d ? lo[i + j] : hi[i + j - d];
+              acc = H.add(acc, H.mul(b[i], b[j]));
+            }
+          for (unsigned j = 0; j < d; ++j) b[j] = H.add(lo[j], H.mul(hi[j], wm));
+        }
+      }
+      const int want = knob::fold_staged();
+      const bool staged = want < 0 ? kFoldStagedDefault : want != 0;
+      begin(st);
+      const hipError_t e = launch_fri_fold<E>(k, d, staged, static_cast<const uint32_t*>(in), static_cast<uint32_t*>(out), A, st);
+      mark(st, "x", k);
+      return rc_of(e);
+    }
+  }
+  // the load form of k_fri_fold without the knob: each thread loads its own fibre.  Measured faster than the
+  // form through LDS in five of six cases at 2^22 rows: the kernel is bound by its
+  // arithmetic, not by the lines its loads touch, and the staging costs occupancy
+  static constexpr bool kFoldStagedDefault = false;
 
   // the engine's fast (quotient-estimate) reduction holds for this modulus in direction F
   static bool fast(const typename E::Args& F) {
@@ -1827,6 +1929,14 @@ int ntt_inverse_matrix_ex(ntt_plan* plan, void* d, unsigned width, const uint64_
 int ntt_lde_matrix_ex(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_blowup, const uint64_t* shift,
                       unsigned width, unsigned order, void* s) {
   return run_matrix(plan, d_in, d_out, width, false, true, log_blowup, shift, order, s);
+}
+// FRI fold: the plan's own engine (never the second plan), one launch
+int ntt_fri_fold(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_rows, unsigned log_arity,
+                 unsigned ext_degree, uint64_t ext_w, const uint64_t* beta, const uint64_t* shift, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.fold(d_in, d_out, log_rows, log_arity, ext_degree, ext_w, beta, shift, S(s));
+  });
 }
 int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;

@@ -62,6 +62,11 @@ inline size_t shim_cache_plans() { return (size_t)(shim_cache_env() > 0 ? shim_c
 // pass kernels accept it (plan_schedule.hpp)
 inline const char* schedule() { return Env("NTT_SCHEDULE").text(); }
 
+// ---- at every ntt_fri_fold call (tools/bench_fold.py times both forms interleaved in one process)
+// NTT_FOLD_STAGED=1 / =0: the fibres of k_fri_fold reach their threads through LDS / each thread loads its
+// own fibre (A/B); unset or empty (-1): the plan's default form
+inline int fold_staged() { return (int)Env("NTT_FOLD_STAGED").num(-1); }
+
 // ---- when a plan first builds its single-launch or in-place state
 // NTT_FUSED_MODE=0: the dataflow form of k_fused3 (per-tile hand-offs), else the grid-barrier form (1)
 inline unsigned fused_mode() { return Env("NTT_FUSED_MODE").is('0') ? 0u : 1u; }

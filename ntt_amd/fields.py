@@ -17,6 +17,11 @@ FIELDS = {
     5: ("KOALABEAR", KOALABEAR, 3),
 }
 
+# The usual binomial extensions F_p[X]/(X^d - W) of the fields a STARK prover folds over, field id -> (d, W):
+# Goldilocks' quadratic and BabyBear's and KoalaBear's quartic extension (each W is a non-residue);
+# NTTPlan.fri_fold takes them as ext_degree and ext_w.
+EXTENSIONS = {3: (2, 7), 4: (4, 11), 5: (4, 3)}
+
 
 def field_params(field_id: int):
     name, p, g = FIELDS[field_id]

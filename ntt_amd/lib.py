@@ -59,6 +59,8 @@ PROTOTYPES = {
     "ntt_forward_matrix_ex": (C.c_int, [_vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
     "ntt_inverse_matrix_ex": (C.c_int, [_vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, _vp]),
     "ntt_lde_matrix_ex": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, C.c_uint, _vp]),
+    "ntt_fri_fold": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_uint64), _vp]),
     "ntt_polymul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ntt_fill": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _vp]),
     "ntt_plan_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_uint),

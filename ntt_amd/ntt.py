@@ -375,6 +375,51 @@ class NTTPlan:
                  "ntt_lde_matrix")
         return out
 
+    def fri_fold(self, evals: torch.Tensor, out: torch.Tensor, log_arity: int, beta: Sequence[int], *,
+                 ext_degree: int = 1, ext_w: int = 0, shift: Optional[int] = None, log_rows: Optional[int] = None,
+                 stream=None) -> torch.Tensor:
+        """One FRI fold of arity 2^log_arity (ntt_fri_fold).  ``evals`` = [N = 2^log_rows][ext_degree] holds
+        the evaluations of a polynomial f with coefficients in F_p[X]/(X^ext_degree - ext_w) on the coset
+        shift*<w_N> with the rows in bit-reversed order, as ``lde_matrix(..., width=ext_degree,
+        bitrev_out=True)`` stores them; ``out`` = [N >> log_arity][ext_degree] receives, in the same order one
+        level down, the evaluations on shift^(2^log_arity)*<w_M> of g = sum_t beta^t f_t, where
+        f(x) = sum_t x^t f_t(x^(2^log_arity)).  ``beta`` is ``ext_degree`` canonical ints; ``log_rows``
+        defaults to the plan's log_n and may be smaller (one plan serves every later layer).  ``evals`` is not
+        modified and must not overlap ``out``; ``fields.EXTENSIONS`` has the usual (ext_degree, ext_w)."""
+        def is_int(v):
+            return isinstance(v, int) and not isinstance(v, bool)
+        if log_rows is None:
+            log_rows = self.log_n
+        if not is_int(log_arity) or not 1 <= log_arity <= 4:
+            raise ValueError(f"log_arity must be an integer in [1, 4], not {log_arity!r}")
+        if not is_int(log_rows) or not log_arity <= log_rows <= self.log_n:
+            raise ValueError(f"log_rows must be an integer in [log_arity, {self.log_n}], not {log_rows!r}")
+        if not is_int(ext_degree) or ext_degree not in (1, 2, 4):
+            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
+        if ext_degree > 1 and (not is_int(ext_w) or not 0 < ext_w < self.p):
+            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
+        try:
+            beta = list(beta)
+        except TypeError:
+            raise ValueError(f"beta must be a sequence of {ext_degree} integers, not {beta!r}") from None
+        if len(beta) != ext_degree or not all(is_int(b) and 0 <= b < self.p for b in beta):
+            raise ValueError(f"beta must be {ext_degree} canonical integers (0 <= beta[j] < p), not {beta!r}")
+        self._check_matrix_ex(shift, True, "")
+        rows, rows_out = 1 << log_rows, 1 << (log_rows - log_arity)
+        self._check_matrix(evals, rows, ext_degree, "evals")
+        self._check_matrix(out, rows_out, ext_degree, "out")
+        a0, b0 = evals.data_ptr(), out.data_ptr()
+        if a0 < b0 + rows_out * ext_degree * self.elem_bytes and b0 < a0 + rows * ext_degree * self.elem_bytes:
+            raise ValueError("evals and out overlap")
+        self._check_matrix_device(evals, "evals")
+        self._check_matrix_device(out, "out")
+        sh = None if shift is None else _u64_array([shift])
+        _L.check(self._lib.ntt_fri_fold(self._h, C.c_void_p(evals.data_ptr()), C.c_void_p(out.data_ptr()),
+                                        int(log_rows), int(log_arity), int(ext_degree),
+                                        int(ext_w) if ext_degree > 1 else 0, _u64_array(beta), sh,
+                                        _stream_ptr(stream, out.device)), "ntt_fri_fold")
+        return out
+
     def matrix_passes(self, width: int) -> List[int]:
         """log2 radices of the passes the matrix calls run at this width (ntt_plan_matrix_info); [] for
         sizes up to 4 rows, which one simple kernel transforms."""
