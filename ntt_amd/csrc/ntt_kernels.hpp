@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "engines.hpp"
+#include "plan_fused.hpp"
 
 namespace ntt {
 
@@ -203,7 +204,8 @@ enum : uint32_t { MAT_REV_IN = 1u, MAT_REV_OUT = 2u, MAT_MUL_OUT = 4u };
 // workgroups through counters instead of kernel boundaries.  Word layout of `sync` (zero before the
 // first launch; the last workgroup to leave re-zeroes it): [0] tile ticket, [1] workgroups exited,
 // [2], [3] spare, [4, 4 + n12) pass 1 -> 2 counters,
-// [4 + n12, 4 + n12 + n23) pass 2 -> final counters, then one ready word per counter (rbase).
+// [4 + n12, 4 + n12 + n23) pass 2 -> final counters, then one ready word per counter (rbase); FusedSync
+// (plan_fused.hpp) has the layout of every form.
 struct FusedArgs {
   uint32_t* sync;
   uint32_t tiles;      // tiles per pass (n / TILE)
@@ -227,6 +229,12 @@ struct FusedArgs {
   uint32_t* shards;            // grid barriers (modes 1..4): 8 arrival shards, one 128-B line each
   unsigned long long* trace;   // diagnostics (NTT_FUSED_TRACE, modes 3 and 4): 4 timestamps per workgroup
 };
+// the engines k_fused3 / k_fused3b / k_fused3bi are instantiated for: those whose fused unit is in build.py's
+// SOURCES (ntt_e256_fused.hip).  The kernels assert the properties they need of it (fused3_props).
+template <class E>
+__host__ __device__ constexpr bool fused3_engine() {
+  return std::is_same_v<E, Eng256>;
+}
 template <class E>
 hipError_t launch_fused3(int r1, int r2, int r3, const uint32_t* src, uint32_t* scratch, uint32_t* dst,
                          const PassArgs<E>& A1, const PassArgs<E>& A2, const PassArgs<E>& A3, const FusedArgs& F,

@@ -16,6 +16,10 @@
 // LDS exchanges (16-B planes) in between: the wave64 replacement for the reference's shared-memory
 // radix-2 rounds (SSIP_NTT_stage1 GZKP-NTT.cu:1297-1357) and its cub::WarpExchange /
 // parallel-load staging (test-cub-WarpExchange.cu:6-64, parallel-load.cu:114-193).
+// This header: the pass tile, k_pass and k_final_ipn, the table builders, the rival schedules and the
+// utility kernels.  Families with translation units of their own live beside it: the single-launch
+// schedules in ntt_fused_impl.hpp, the row-major matrix passes in ntt_mat_impl.hpp, the FRI fold in
+// ntt_fold_impl.hpp.
 #pragma once
 #include <cstdlib>
 #include <utility>
@@ -34,6 +38,19 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// The launchers' radix dispatch: f(std::integral_constant<int, R>{}) for the run-time logr = R in
+// [LO, HI], hipErrorInvalidValue outside.  (Host code: static_for above is the device's.)
+template <int LO, class F, int... I>
+hipError_t with_radix_impl(int logr, F&& f, std::integer_sequence<int, I...>) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((logr == LO + I ? (e = f(std::integral_constant<int, LO + I>{}), true) : false) || ...);
+  return e;
+}
+template <int LO, int HI, class F>
+hipError_t with_radix(int logr, F&& f) {
+  return with_radix_impl<LO>(logr, f, std::make_integer_sequence<int, HI - LO + 1>{});
 }
 
 __host__ __device__ constexpr int brev_bits(int v, int bits) {
@@ -386,8 +403,8 @@ __device__ __forceinline__ bool grid_barrier_words(uint32_t* top, uint32_t* shar
   __syncthreads();
   return __builtin_amdgcn_readfirstlane(s_ok) != 0u;
 }
-// The in-place single launch's last barrier (the K-th of the launch: 4 in k_fused3bi, 3 in
-// k_fused2bi), between every final tile's loads and any store (PassArgs: ipn_sync = the top counter,
+// The in-place single launch's last barrier (the K-th of the launch: FUSED3BI_BARRIERS in k_fused3bi,
+// FUSED2BI_BARRIERS in k_fused2bi), between every final tile's loads and any store (PassArgs: ipn_sync = the top counter,
 // ipn_shards = the shard lines, ipn_go = the go word)
 template <uint32_t K, class E>
 __device__ __forceinline__ bool ipn_grid_barrier(const PassArgs<E>& A) {
@@ -471,27 +488,44 @@ __host__ __device__ constexpr bool pass_ltw() {
 
 // One workgroup tile of one pass: tile w (the workgroup index of a k_pass launch) of transform bq
 // (its blockIdx.y).  lds: pass_lds_words() words, lds_tw: 2^LOGR E::TW words when pass_ltw().  k_pass runs
-// one tile per workgroup; the fused single-launch schedule (k_fused3) runs several passes' tiles
-// in one persistent workgroup.
+// one tile per workgroup; the fused single-launch schedule (k_fused3, ntt_fused_impl.hpp) runs several
+// passes' tiles in one persistent workgroup.
 // LOOPED (persistent workgroups, k_fused3): the thread index is re-read per tile through an opaque
 // copy, so that the compiler does not hoist every lane-dependent address out of the tile loop (held in
 // VGPRs across the whole loop, they spilled 200-380 B per thread; per tile they cost a few VALU ops).
 // IPN (final pass of an in-place plan): outputs go to their natural positions in the same buffer.
-// 1 (k_final_ipn): a tile's loads are counted in per slab, and its stores wait until the mirror slab
-// has been read.  2 / 3 (k_fused3bi / k_fused2bi, every final tile resident): a grid barrier between
-// all loads and all stores.  4 (pass 1 of k_fused3bi / k_fused2bi): the stores wait for the launch's
-// residency decision (residency_wait) and are skipped when it was abandoned.
-// MAT (k_pass_mat, the ntt_*_matrix calls): the strip form.  The tile is Mode I with il = A.il on strip
+// IPN_SLAB (k_final_ipn): a tile's loads are counted in per slab, and its stores wait until the mirror
+// slab has been read.  IPN_FUSED3 / IPN_FUSED2 (k_fused3bi / k_fused2bi, every final tile resident):
+// a grid barrier, the launch's last, between all loads and all stores.  IPN_RESIDENCY (pass 1 of
+// k_fused3bi / k_fused2bi): the stores wait for the launch's residency decision (residency_wait) and
+// are skipped when it was abandoned.
+// MAT (k_pass_mat in ntt_mat_impl.hpp, the ntt_*_matrix calls): the strip form.  The tile is Mode I with il = A.il on strip
 // bq of a row-major [n][A.mat_w] matrix: (TILE >> il) transform positions by 2^il adjacent columns, the
 // interleaved index P = row 2^il + bl standing for element (row, bq 2^il + bl) at row A.mat_w + that
 // column -- a multiply where Mode I shifts.  Twiddle indices depend on the row alone.  Columns at and
 // past A.mat_w (the last strip of a row) do not exist: their lanes load nothing, carry zeros through
 // the tile and store nothing.
+enum : int { IPN_NONE = 0, IPN_SLAB = 1, IPN_FUSED3 = 2, IPN_FUSED2 = 3, IPN_RESIDENCY = 4 };
+// Names for pass_tile's options, in the order of its template parameters: no call site passes a bare
+// true / false / 0.  (They stay positional values of the types below.  Gathering them into one options
+// type, or calling through a wrapper that takes one, changed the register allocation of 29-bit-engine
+// kernels -- tools/kernel_manifest.py -- and was taken out again.)
+constexpr bool TW_FULL = true, TW_TWO_LEVEL = false;    // FULLTW: a full outer-twiddle table / the two-level tables
+constexpr bool RED_FAST = true, RED_GENERIC = false;    // FAST: unnormalised butterflies and fast reductions
+constexpr bool SRC_CALLER = true, SRC_SCRATCH = false;  // SRC_USER: a column pass's source layout
+enum : int { FSM_NONE = 0, FSM_MAPS = 1, FSM_EPILOGUE = 2 };  // FSM
+constexpr bool OUTER_SHOUP = true, OUTER_MONT = false;  // SHTW: the full table holds Shoup pairs / w R_e
+constexpr bool STORE_WT = true, STORE_PLAIN = false;    // WT: write-through stores (read by another workgroup)
+constexpr bool TILE_LOOPED = true, TILE_ONCE = false;   // LOOPED: several tiles per workgroup
+constexpr bool STRIP_FORM = true;                       // MAT
 template <class E, int LOGR, int KIND, bool FULLTW, bool FAST, int PRO = PRO_NONE, bool SRC_USER = true,
           int FSM = 0, bool SHTW = false, bool WT = false, bool LOOPED = false, int IPN = 0, bool MAT = false>
 __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                           const PassArgs<E>& A, const uint32_t w, const uint32_t bq,
                                           uint32_t* __restrict__ lds, uint32_t* __restrict__ lds_tw) {
+  static_assert(!SHTW || (FULLTW && KIND == KIND_COLUMN), "Shoup pairs: a column pass's full table");
+  static_assert(!WT || KIND == KIND_COLUMN, "write-through stores: scratch");
+  static_assert(IPN == IPN_NONE || (IPN == IPN_RESIDENCY ? KIND == KIND_COLUMN && WT : KIND == KIND_FINAL), "IPN forms");
   constexpr int QB = ept_log<E>(), EPT = E::EPT;
   using S = Sched<LOGR, QB>;
   constexpr bool COLLIKE = KIND == KIND_COLUMN || KIND == KIND_STOCKHAM || KIND == KIND_DIT;  // column groups
@@ -768,7 +802,7 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
     }
   }
 
-  if constexpr (IPN == 1) ipn_signal_read(A, mid);  // this tile's elements are in registers now
+  if constexpr (IPN == IPN_SLAB) ipn_signal_read(A, mid);  // this tile's elements are in registers now
 
   // ------------------------------------------------------------------ sub-stages 1..nsub-1 via LDS
   if constexpr (S::nsub > 1) substage<E, LOGR, T, TE, NT, 1, FAST, R32, LTW>(x, cl, pil, lds, A, t, lds_tw, w);
@@ -779,11 +813,11 @@ __device__ __forceinline__ void pass_tile(const uint32_t* __restrict__ src, uint
   static_assert(S::nsub <= 6, "sub-stages");
 
   // ------------------------------------------------------------------ output
-  if constexpr (IPN == 1) {  // the slab this tile writes into has been read (or the wait gave up: no stores)
+  if constexpr (IPN == IPN_SLAB) {  // the slab this tile writes into has been read (or the wait gave up: no stores)
     if (!ipn_wait_mirror(A, midrev)) return;
-  } else if constexpr (IPN == 2 || IPN == 3) {  // in-place single launch: every final tile has read (grid barrier)
-    if (!ipn_grid_barrier<IPN == 2 ? 4u : 3u>(A)) return;
-  } else if constexpr (IPN == 4) {  // in-place single launch, pass 1: every workgroup is resident (A.ipn_go)
+  } else if constexpr (IPN == IPN_FUSED3 || IPN == IPN_FUSED2) {  // in-place single launch: every final tile has read
+    if (!ipn_grid_barrier<IPN == IPN_FUSED3 ? FUSED3BI_BARRIERS : FUSED2BI_BARRIERS>(A)) return;
+  } else if constexpr (IPN == IPN_RESIDENCY) {  // in-place single launch, pass 1: every workgroup is resident (A.ipn_go)
     if (!residency_wait(A.ipn_go, A.wd)) return;
   }
   {
@@ -938,14 +972,14 @@ void k_final_ipn(uint32_t* data, const PassArgs<E> A) {
   const uint32_t w = s_w;
   if constexpr (E::FASTRED) {
     if (A.F.red_ok)
-      pass_tile<E, LOGR, KIND_FINAL, false, true, PRO_NONE, true, 0, false, false, false, 1>(data, data, A, w, 0, lds,
-                                                                                           lds_tw);
+      pass_tile<E, LOGR, KIND_FINAL, TW_TWO_LEVEL, RED_FAST, PRO_NONE, SRC_CALLER, FSM_NONE, OUTER_MONT, STORE_PLAIN, TILE_ONCE, IPN_SLAB>(
+          data, data, A, w, 0, lds, lds_tw);
     else
-      pass_tile<E, LOGR, KIND_FINAL, false, false, PRO_NONE, true, 0, false, false, false, 1>(data, data, A, w, 0,
-                                                                                            lds, lds_tw);
+      pass_tile<E, LOGR, KIND_FINAL, TW_TWO_LEVEL, RED_GENERIC, PRO_NONE, SRC_CALLER, FSM_NONE, OUTER_MONT, STORE_PLAIN, TILE_ONCE, IPN_SLAB>(
+          data, data, A, w, 0, lds, lds_tw);
   } else {
-    pass_tile<E, LOGR, KIND_FINAL, false, false, PRO_NONE, true, 0, false, false, false, 1>(data, data, A, w, 0, lds,
-                                                                                          lds_tw);
+    pass_tile<E, LOGR, KIND_FINAL, TW_TWO_LEVEL, RED_GENERIC, PRO_NONE, SRC_CALLER, FSM_NONE, OUTER_MONT, STORE_PLAIN, TILE_ONCE, IPN_SLAB>(
+        data, data, A, w, 0, lds, lds_tw);
   }
   if (t == 0)
     s_last = __hip_atomic_fetch_add(A.ipn_sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
@@ -963,520 +997,37 @@ void k_final_ipn(uint32_t* data, const PassArgs<E> A) {
   }
 }
 
+// The host function of k_final_ipn<E, logr>, or null where the radix has no instance: the launcher and
+// the capacity query take their kernel from here
+template <class E>
+auto final_ipn_kernel(int logr) -> void (*)(uint32_t*, const PassArgs<E>) {
+  void (*k)(uint32_t*, const PassArgs<E>) = nullptr;
+  (void)with_radix<3, 9>(logr, [&](auto R) {
+    if constexpr (R <= tile_log_of<E>() - E::MIN_COLS_LOG) k = &k_final_ipn<E, R>;
+    return hipSuccess;
+  });
+  return k;
+}
+
 template <class E>
 hipError_t launch_final_ipn(int logr, uint32_t* data, const PassArgs<E>& A, uint32_t grid, hipStream_t st) {
-  constexpr int TL = tile_log_of<E>();
-  constexpr int NT = (1 << TL) / E::EPT;
-  switch (logr) {
-#define NTT_IPN_CASE(R)                                                                          \
-  case R:                                                                                        \
-    if constexpr (R <= TL - E::MIN_COLS_LOG) {                                                   \
-      hipLaunchKernelGGL((k_final_ipn<E, R>), dim3(grid), dim3(NT), 0, st, data, A);             \
-      return hipGetLastError();                                                                  \
-    }                                                                                            \
-    return hipErrorInvalidValue;
-    NTT_IPN_CASE(3)
-    NTT_IPN_CASE(4)
-    NTT_IPN_CASE(5)
-    NTT_IPN_CASE(6)
-    NTT_IPN_CASE(7)
-    NTT_IPN_CASE(8)
-    NTT_IPN_CASE(9)
-#undef NTT_IPN_CASE
-    default: return hipErrorInvalidValue;
-  }
+  const auto k = final_ipn_kernel<E>(logr);
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(grid), dim3((1 << tile_log_of<E>()) / E::EPT), 0, st, data, A);
+  return hipGetLastError();
 }
 
 // Workgroups of k_final_ipn<E, logr> the device keeps resident at once (occupancy x CUs; 0 if the
 // query fails or the radix has no instance)
 template <class E>
 uint32_t launch_final_ipn_capacity(int logr, int device) {
-  constexpr int TL = tile_log_of<E>();
-  constexpr int NT = (1 << TL) / E::EPT;
   int cus = 0, per = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
-  hipError_t e = hipErrorInvalidValue;
-  switch (logr) {
-#define NTT_IPN_OCC(R)                                                                                   \
-  case R:                                                                                                \
-    if constexpr (R <= TL - E::MIN_COLS_LOG)                                                             \
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(&k_final_ipn<E, R>), NT, 0); \
-    break;
-    NTT_IPN_OCC(3)
-    NTT_IPN_OCC(4)
-    NTT_IPN_OCC(5)
-    NTT_IPN_OCC(6)
-    NTT_IPN_OCC(7)
-    NTT_IPN_OCC(8)
-    NTT_IPN_OCC(9)
-#undef NTT_IPN_OCC
-    default: break;
-  }
-  return (e == hipSuccess && per > 0 && cus > 0) ? (uint32_t)per * (uint32_t)cus : 0u;
-}
-
-// ---------------------------------------------------------------------------- fused 3-pass launch
-// BASELINE config 2 asks for the 2^20 transform as a single kernel (the reference's SSIP schedule is
-// 4 launches at 2^20, GZKP-NTT.cu:1509-1545).  k_fused3 runs the three passes of a 3-pass schedule in
-// ONE persistent launch.  Workgroups take tiles from one ticket counter in pass-major order (pass 1's
-// tiles, then pass 2's, then the final pass's); a tile waits only for the tiles it reads, through
-// counters keyed by the dependency structure of the four-step passes:
-//   * pass-2 tile (block k1, column group g) reads columns g T2 + [0, T2) + s2 j2 of every j2 < R2,
-//     written by the pass-1 tiles whose columns mod s2 (= 2^r3) fall in the same U-column unit
-//     (U = max(T1, T2)): s2 / U counters, each reached by (U / T1) R2 pass-1 tiles;
-//   * a final tile (T3 adjacent k1, one k2) reads every column of those k1 blocks: counters keyed by
-//     k1 >> log T3 (R1 / T3 of them), each reached by T3 (s2 / T2) pass-2 tiles.
-// Deadlock-free at any residency: a tile waits only for tiles with smaller tickets, which are held
-// by running workgroups whose own waits are on smaller tickets still (pass 1 waits on nothing).
-// Hand-off (MI355X_MICROARCH.md § visibility, publish form R1): scratch stores are write-through
-// (sc1), every wave drains them (s_waitcnt vmcnt(0)), a workgroup barrier, then one lane's agent-scope
-// counter add; the group's last arrival raises a ready word; the consumer polls it, takes ONE
-// agent-scope acquire, waits, barrier, plain loads.
-// Every dependency wait is bounded (Watchdog: a workgroup whose wait gives up runs no further tile,
-// the launch's other waits give up at once, and the plan's next call returns NTT_ERR_DEVICE), so every
-// wave reaches the exit; the last workgroup out re-zeroes the counters for the next launch.
-// Producer: every wave drains its write-through stores, a barrier, then one lane counts the tile in;
-// the group's last arrival (told by the value its add returns) raises the group's ready word, which
-// lies on a 128-B line of its own.  Consumers poll only that word: 128 pollers on the counter itself
-// queued the producers' adds behind their polls (2^20: 350-450 us per transform instead of 160).
-__device__ __forceinline__ void fused_publish(uint32_t* cnt, uint32_t* ready, uint32_t need) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its write-through stores are done
-  __syncthreads();
-  if (threadIdx.x == 0 && __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == need - 1)
-    __hip_atomic_store(ready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// Consumer: one lane polls the ready word with relaxed agent-scope loads (compare-exchange polls,
-// read-modify-writes at the memory side, queued the producers' updates behind them: 2^20 single
-// launch 0.162 -> see DESIGN §4), sleeping 60 ns .. 1 us between polls; then ONE agent-scope acquire, its wait, and
-// the workgroup barrier before any load of the handed-off tile.  Bounded (Watchdog): false
-// (workgroup-uniform) when the wait gave up; the workgroup then runs no further tile.
-__device__ __forceinline__ bool fused_wait(uint32_t* ready, const FusedArgs& F) {
-  if (F.dbg & 1u) return true;  // diagnostics only: no dependency waits (wrong output)
-  __shared__ uint32_t s_ok;
-  if (threadIdx.x == 0) {
-    s_ok = poll_bounded<2, 4, 8, 16, 32>(ready, F.wd) ? 1u : 0u;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-  return __builtin_amdgcn_readfirstlane(s_ok) != 0u;
-}
-
-template <class E>
-struct FusedKArgs {
-  const uint32_t* src;
-  uint32_t* scratch;
-  uint32_t* dst;
-  PassArgs<E> A1, A2, A3;
-  FusedArgs F;
-};
-static_assert(sizeof(FusedKArgs<Eng256>) <= 4096, "kernel argument segment");
-// The kernel arguments re-addressed per tile through an opaque copy of the kernarg pointer, so that
-// the persistent loops do not keep every pass's uniform arguments live across the loop (with the
-// LOOPED thread index above: 0-16 B of spills instead of 200-380 B).
-template <class E>
-__device__ __forceinline__ const FusedKArgs<E>& fused_kargs() {
-  typedef const __attribute__((address_space(4))) FusedKArgs<E>* KP;
-  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return *(const FusedKArgs<E>*)p;
-}
-
-template <class E, int R1, int R2, int R3>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_fused3(const FusedKArgs<E> K) {
-  static_assert(E::FASTRED && E::SHOUP_OUTER && !E::LDS_TW, "fused schedule: FAST 256-bit engines");
-  constexpr int LW = pass_lds_words<E, R1, KIND_COLUMN>();
-  static_assert(LW == pass_lds_words<E, R3, KIND_FINAL>(), "one tile size");
-  __shared__ __attribute__((aligned(16))) uint32_t lds[LW];
-  __shared__ uint32_t lds_tw[1];
-  __shared__ uint32_t s_ticket;
-  const FusedArgs& F = K.F;
-  uint32_t* const cnt12 = F.sync + 4;
-  uint32_t* const cnt23 = F.sync + 4 + F.n12;
-  const uint32_t t = threadIdx.x, total = 3 * F.tiles;
-  // Tile order: every tile is a ticket sync[0]++, the first taken at start, each later one while the
-  // previous tile's stores drain, i.e. in completion order.  (A ticket prefetched at tile START let
-  // the first workgroups to start take two or three pass-1 tiles each while later ones idled on
-  // pass-2 tiles: 4x slower at 2^20.)
-  uint32_t stat = blockIdx.x;  // dbg bit 2: static order b, b + nwg, ...
-  auto ticket = [&]() -> uint32_t {
-    if (F.dbg & 4u) return stat += F.nwg;
-    return t == 0 ? __hip_atomic_fetch_add(F.sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  };
-  if (t == 0) s_ticket = (F.dbg & 4u) ? blockIdx.x : ticket();
-  __syncthreads();
-  uint32_t tk = s_ticket;
-  auto advance = [&](uint32_t next) {
-    __syncthreads();  // every wave is done with this tile's LDS and s_ticket
-    if (t == 0) s_ticket = next;
-    __syncthreads();
-    tk = s_ticket;
-  };
-  // tickets only grow per workgroup and are handed out pass-major: one loop per pass
-  while (tk < F.tiles) {  // pass 1: the caller's buffer -> scratch
-    const uint32_t w = tk;
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R1, KIND_COLUMN, true, true, PRO_NONE, true, 0, false, true, true>(L.src, L.scratch, L.A1, w, 0,
-                                                                                      lds, lds_tw);
-    const uint32_t next = ticket();  // issued before the drain of this tile's stores
-    const uint32_t key = (w & F.k1_mask) >> F.k1_shift;
-    fused_publish(cnt12 + key, F.sync + F.rbase + 32 * key, F.need12);
-    advance(next);
-  }
-  while (tk < 2 * F.tiles) {  // pass 2: scratch in place (Shoup-pair outer twiddles)
-    const uint32_t w = tk - F.tiles, g = w & ((1u << F.cg_log) - 1);
-    if (!fused_wait(F.sync + F.rbase + 32 * (g >> F.k2_shift), F)) {
-      tk = total;  // gave up (watchdog): no further tile, straight to the exit
-      break;
-    }
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R2, KIND_COLUMN, true, true, PRO_NONE, true, 0, true, true, true>(L.scratch, L.scratch, L.A2, w, 0,
-                                                                                     lds, lds_tw);
-    const uint32_t next = ticket();
-    const uint32_t key = (w >> F.cg_log) >> F.t3_log;
-    fused_publish(cnt23 + key, F.sync + F.rbase + 32 * (F.n12 + key), F.need23);
-    advance(next);
-  }
-  while (tk < total) {  // final pass: scratch -> the caller's buffer, natural order
-    const uint32_t w = tk - 2 * F.tiles;
-    if (!fused_wait(F.sync + F.rbase + 32 * (F.n12 + (w >> F.r2)), F)) break;
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R3, KIND_FINAL, false, true, PRO_NONE, true, 0, false, false, true>(L.scratch, L.dst, L.A3, w, 0,
-                                                                                       lds, lds_tw);
-    advance(ticket());
-  }
-  if (t == 0 && __hip_atomic_fetch_add(F.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == F.nwg - 1) {
-    // the last workgroup out: nobody touches the counters again in this launch
-    const uint32_t words = F.rbase + 32 * (F.n12 + F.n23);
-    for (uint32_t i = 0; i < words; ++i) __hip_atomic_store(F.sync + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (F.wd.abort) __hip_atomic_store(F.wd.abort, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// The same three passes with two grid-wide barriers instead of per-tile hand-offs (FusedArgs::mode 1,
-// a plain launch of at most the workgroups the device holds at once).  Each workgroup runs tiles b, b + G, ... of a
-// pass, then the barrier.  The barrier (the guide's R1 publish, MI355X_MICROARCH.md § visibility):
-// * scratch stores are write-through (sc1), so no release fence: every wave drains them, then a
-//   workgroup barrier, then one lane counts the workgroup in;
-// * the last of the G arrivals raises the barrier's go word (its own 128-B line);
-// * one lane per workgroup polls that word with relaxed global loads (bounded: then the watchdog
-//   word), takes ONE agent-scope acquire, and the workgroup barrier releases every wave.
-// A/B: plain stores with an agent-scope release per workgroup were slower at 2^20
-// (every release writes back its XCD's L2), and compare-exchange polls of one word by 1024
-// workgroups made each barrier cost ~0.15 ms.
-// The arrival counter is cumulative (barrier k completes at k G arrivals); the last workgroup out
-// re-zeroes the words for the next launch.
-// False (workgroup-uniform) when the wait gave up (Watchdog): the workgroup then skips the passes left.
-__device__ __forceinline__ bool fused_grid_barrier(const FusedArgs& F, uint32_t k) {
-  return grid_barrier_words(F.sync, F.shards, F.sync + F.rbase + 32 * (k - 1), k, F.wd);
-}
-
-template <class E, int R1, int R2, int R3>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_fused3b(const FusedKArgs<E> K) {
-  static_assert(E::FASTRED && E::SHOUP_OUTER && !E::LDS_TW, "fused schedule: FAST 256-bit engines");
-  constexpr int LW = pass_lds_words<E, R1, KIND_COLUMN>();
-  static_assert(LW == pass_lds_words<E, R3, KIND_FINAL>(), "one tile size");
-  __shared__ __attribute__((aligned(16))) uint32_t lds[LW];
-  __shared__ uint32_t lds_tw[1];
-  const FusedArgs& F = K.F;
-  const uint32_t G = gridDim.x;
-  for (uint32_t w = blockIdx.x; w < F.tiles; w += G) {  // pass 1: the caller's buffer -> scratch
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R1, KIND_COLUMN, true, true, PRO_NONE, true, 0, false, true, true>(L.src, L.scratch, L.A1,
-                                                                                                w, 0, lds, lds_tw);
-    __syncthreads();  // every wave is done with this tile's LDS
-  }
-  bool ok = fused_grid_barrier(F, 1);
-  for (uint32_t w = blockIdx.x; ok && w < F.tiles; w += G) {  // pass 2: scratch in place
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R2, KIND_COLUMN, true, true, PRO_NONE, true, 0, true, true, true>(L.scratch, L.scratch, L.A2,
-                                                                                               w, 0, lds, lds_tw);
-    __syncthreads();
-  }
-  ok = ok && fused_grid_barrier(F, 2);  // a workgroup that gave up does not arrive: the others give up too
-  for (uint32_t w = blockIdx.x; ok && w < F.tiles; w += G) {  // final pass: scratch -> the caller's buffer
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R3, KIND_FINAL, false, true, PRO_NONE, true, 0, false, false, true>(L.scratch, L.dst, L.A3, w, 0,
-                                                                                       lds, lds_tw);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && __hip_atomic_fetch_add(F.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
-    // the last workgroup out: every other one has passed both barriers
-    __hip_atomic_store(F.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (F.wd.abort) __hip_atomic_store(F.wd.abort, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + F.rbase, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + F.rbase + 32, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t sh = 0; sh < 8; ++sh) __hip_atomic_store(F.shards + 32 * sh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// The single-launch schedule of an NTT_PLAN_IN_PLACE plan (FusedArgs::mode 2; BASELINE config 2's
-// "single-kernel self-sort-in-place"): no scratch, every pass in the caller's buffer.  Passes 1 and 2
-// write the positions they read (write-through, as k_fused3b); the final pass of the palindromic
-// schedule writes its outputs to their natural positions, which lie in the mirror slab, so every final
-// tile loads and transforms, a third grid barrier makes sure every tile has read, and only then do the
-// tiles store (IPN = 2 in pass_tile).  That needs every final tile resident at once: one tile per
-// workgroup, nwg == tiles (n <= 2^20 at 4 workgroups per CU), and a residency check before the first
-// store (residency_arrive / residency_wait: barrier 1), so that a launch whose workgroups are not all
-// resident stores nothing.
-template <class E, int R1, int R2, int R3>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_fused3bi(const FusedKArgs<E> K) {
-  static_assert(E::FASTRED && E::SHOUP_OUTER && !E::LDS_TW && E::SCRW == E::MEMW, "fused in place: 256-bit engines");
-  constexpr int LW = pass_lds_words<E, R1, KIND_COLUMN>();
-  static_assert(LW == pass_lds_words<E, R3, KIND_FINAL>(), "one tile size");
-  __shared__ __attribute__((aligned(16))) uint32_t lds[LW];
-  __shared__ uint32_t lds_tw[1];
-  const FusedArgs& F = K.F;
-  const uint32_t G = gridDim.x;
-  uint32_t* const go1 = F.sync + F.rbase;  // residency: grid barrier 1 (residency_arrive)
-  residency_arrive(F.sync, F.shards, go1);
-  for (uint32_t w = blockIdx.x; w < F.tiles; w += G) {  // pass 1, in place; its stores wait for residency
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R1, KIND_COLUMN, true, true, PRO_NONE, true, 0, false, true, true, 4>(L.dst, L.dst, L.A1, w, 0, lds,
-                                                                                         lds_tw);
-    __syncthreads();
-  }
-  bool ok = residency_went(go1) && fused_grid_barrier(F, 2);
-  for (uint32_t w = blockIdx.x; ok && w < F.tiles; w += G) {  // pass 2, in place
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R2, KIND_COLUMN, true, true, PRO_NONE, true, 0, true, true, true>(L.dst, L.dst, L.A2, w, 0, lds,
-                                                                                     lds_tw);
-    __syncthreads();
-  }
-  ok = ok && fused_grid_barrier(F, 3);
-  if (ok && blockIdx.x < F.tiles) {  // final pass: load, transform, barrier 4 (inside), natural-order stores
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R3, KIND_FINAL, false, true, PRO_NONE, true, 0, false, false, true, 2>(L.dst, L.dst, L.A3,
-                                                                                         blockIdx.x, 0, lds, lds_tw);
-  }
-  if (threadIdx.x == 0 && __hip_atomic_fetch_add(F.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
-    // the last workgroup out: every other one has passed (or given up at) all four barriers
-    __hip_atomic_store(F.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (F.wd.abort) __hip_atomic_store(F.wd.abort, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t k = 0; k < 4; ++k)
-      __hip_atomic_store(F.sync + F.rbase + 32 * k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t sh = 0; sh < 8; ++sh) __hip_atomic_store(F.shards + 32 * sh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// BASELINE config 2 as ONE kernel on 4096-element tiles (the reference's 2^20
-// schedule is 4 launches, GZKP-NTT.cu:1509-1545): the two passes (10 + 10) of Eng256T with ONE grid
-// barrier between them.  2^20 is 256 tiles per pass, one 1024-thread workgroup per CU, so each
-// workgroup runs one tile of each pass.  A plain launch (no cooperative launch: its ~20 us per call
-// was most of the 3-pass single launch's deficit) of at most the occupancy query's
-// workgroups; the barrier is bounded (Watchdog), so a device shared with another persistent kernel
-// ends in NTT_ERR_DEVICE, never a hang.
-//   k_fused2b  (FusedArgs::mode 3): pass 1 caller -> scratch (write-through), barrier, final pass
-//              scratch -> caller, natural order.
-//   k_fused2bi (FusedArgs::mode 4): NTT_PLAN_IN_PLACE, the palindromic 10 + 10: pass 1 in place (its
-//              stores wait for the residency decision, barrier 1), barrier 2, the final pass loads and
-//              transforms every tile, barrier 3 (every tile has read: all 256 final tiles are
-//              resident), then the stores to the natural positions in the mirror slab (pass_tile
-//              IPN = 3).  No scratch.
-// FusedArgs::trace (diagnostics, NTT_FUSED_TRACE): per workgroup the wall clock (100 MHz) at start,
-// after pass 1, after the pass barrier and at the end.
-__device__ __forceinline__ void fused_trace(const FusedArgs& F, uint32_t at) {
-  if (F.trace && threadIdx.x == 0) F.trace[4 * blockIdx.x + at] = (unsigned long long)wall_clock64();
-}
-template <class E, int R1, int R2>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_fused2b(const FusedKArgs<E> K) {
-  static_assert(E::FASTRED && !E::LDS_TW, "fused schedule: FAST 256-bit engines");
-  constexpr int LW = pass_lds_words<E, R1, KIND_COLUMN>();
-  static_assert(LW == pass_lds_words<E, R2, KIND_FINAL>(), "one tile size");
-  __shared__ __attribute__((aligned(16))) uint32_t lds[LW];
-  __shared__ uint32_t lds_tw[1];
-  const FusedArgs& F = K.F;
-  const uint32_t G = gridDim.x;
-  fused_trace(F, 0);
-  for (uint32_t w = blockIdx.x; w < F.tiles; w += G) {  // pass 1: the caller's buffer -> scratch
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R1, KIND_COLUMN, true, true, PRO_NONE, true, 0, false, true, true>(L.src, L.scratch, L.A1, w, 0, lds,
-                                                                                      lds_tw);
-    __syncthreads();
-  }
-  fused_trace(F, 1);
-  const bool ok = fused_grid_barrier(F, 1);
-  fused_trace(F, 2);
-  for (uint32_t w = blockIdx.x; ok && w < F.tiles; w += G) {  // final pass: scratch -> the caller's buffer
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R2, KIND_FINAL, false, true, PRO_NONE, true, 0, false, false, true>(L.scratch, L.dst, L.A3, w, 0, lds,
-                                                                                      lds_tw);
-    __syncthreads();
-  }
-  fused_trace(F, 3);
-  if (threadIdx.x == 0 && __hip_atomic_fetch_add(F.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
-    // the last workgroup out: every other one has passed (or given up at) the barrier
-    __hip_atomic_store(F.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (F.wd.abort) __hip_atomic_store(F.wd.abort, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + F.rbase, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t sh = 0; sh < 8; ++sh) __hip_atomic_store(F.shards + 32 * sh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-template <class E, int R>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_fused2bi(const FusedKArgs<E> K) {
-  static_assert(E::FASTRED && !E::LDS_TW && E::SCRW == E::MEMW, "fused in place: 256-bit engines");
-  constexpr int LW = pass_lds_words<E, R, KIND_COLUMN>();
-  static_assert(LW == pass_lds_words<E, R, KIND_FINAL>(), "one tile size");
-  __shared__ __attribute__((aligned(16))) uint32_t lds[LW];
-  __shared__ uint32_t lds_tw[1];
-  const FusedArgs& F = K.F;
-  const uint32_t G = gridDim.x;
-  uint32_t* const go1 = F.sync + F.rbase;  // residency: grid barrier 1 (residency_arrive)
-  fused_trace(F, 0);
-  residency_arrive(F.sync, F.shards, go1);
-  for (uint32_t w = blockIdx.x; w < F.tiles; w += G) {  // pass 1, in place; its stores wait for residency
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R, KIND_COLUMN, true, true, PRO_NONE, true, 0, false, true, true, 4>(L.dst, L.dst, L.A1, w, 0, lds,
-                                                                                        lds_tw);
-    __syncthreads();
-  }
-  fused_trace(F, 1);
-  const bool ok = residency_went(go1) && fused_grid_barrier(F, 2);
-  fused_trace(F, 2);
-  if (ok && blockIdx.x < F.tiles) {  // final pass: load, transform, barrier 3 (inside), natural-order stores
-    const FusedKArgs<E>& L = fused_kargs<E>();
-    pass_tile<E, R, KIND_FINAL, false, true, PRO_NONE, true, 0, false, false, true, 3>(L.dst, L.dst, L.A3, blockIdx.x, 0,
-                                                                                        lds, lds_tw);
-  }
-  fused_trace(F, 3);
-  if (threadIdx.x == 0 && __hip_atomic_fetch_add(F.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
-    __hip_atomic_store(F.sync, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(F.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (F.wd.abort) __hip_atomic_store(F.wd.abort, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t k = 0; k < 3; ++k)
-      __hip_atomic_store(F.sync + F.rbase + 32 * k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (uint32_t sh = 0; sh < 8; ++sh) __hip_atomic_store(F.shards + 32 * sh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-template <class E>
-hipError_t launch_fused2(int r1, int r2, const uint32_t* src, uint32_t* scratch, uint32_t* dst, const PassArgs<E>& A1,
-                         const PassArgs<E>& A2, const FusedArgs& F, hipStream_t st) {
-  if constexpr (!fused2_engine<E>()) {
-    return hipErrorInvalidValue;
-  } else {
-    if (r1 != 10 || r2 != 10 || (F.mode != 3 && F.mode != 4)) return hipErrorInvalidValue;
-    const dim3 g(F.nwg), b((1 << E::TILE_LOG) / E::EPT);
-    FusedKArgs<E> K{src, scratch, dst, A1, A1, A2, F};
-    if (F.mode == 4)
-      hipLaunchKernelGGL((k_fused2bi<E, 10>), g, b, 0, st, K);
-    else
-      hipLaunchKernelGGL((k_fused2b<E, 10, 10>), g, b, 0, st, K);
-    return hipGetLastError();
-  }
-}
-// workgroups of k_fused2b (mode 3) / k_fused2bi (mode 4) resident at once on `device`
-template <class E>
-hipError_t fused2_capacity(int r1, int r2, int device, uint32_t* wgs, uint32_t mode) {
-  if constexpr (!fused2_engine<E>()) {
-    return hipErrorInvalidValue;
-  } else {
-    if (r1 != 10 || r2 != 10) return hipErrorInvalidValue;
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return hipErrorInvalidValue;
-    const int threads = (1 << E::TILE_LOG) / E::EPT;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per, mode == 4 ? reinterpret_cast<const void*>(&k_fused2bi<E, 10>) : reinterpret_cast<const void*>(&k_fused2b<E, 10, 10>),
-        threads, 0);
-    if (e != hipSuccess) return e;
-    *wgs = (uint32_t)(cus * per);
-    return hipSuccess;
-  }
-}
-
-template <class E>
-hipError_t launch_fused3(int r1, int r2, int r3, const uint32_t* src, uint32_t* scratch, uint32_t* dst,
-                         const PassArgs<E>& A1, const PassArgs<E>& A2, const PassArgs<E>& A3, const FusedArgs& F,
-                         hipStream_t st) {
-  if constexpr (!(E::FASTRED && E::SHOUP_OUTER && !E::LDS_TW && E::TILE_LOG == 10 && E::EPT == 4)) {
-    return hipErrorInvalidValue;
-  } else {
-    const dim3 g(F.nwg), b((1 << E::TILE_LOG) / E::EPT);
-    FusedKArgs<E> K{src, scratch, dst, A1, A2, A3, F};
-    // The grid-barrier forms are plain launches of at most the occupancy query's workgroups (the plan
-    // checks that the grid fits the device, fused3_capacity); the plan serialises its single launches
-    // per device (ntt_plan.cpp FusedSerial), and the in-place form checks residency before its first
-    // store.  Round 6 retired the cooperative launch: ~20 us more per call, and every
-    // rocprofv3-traced process that had made one crashed in the runtime's exit handlers.
-    if (F.mode == 2) {  // in place: one workgroup per tile
-#define NTT_FUSED_IP_CASE(a, c, d)                                                                \
-  if (r1 == a && r2 == c && r3 == d) {                                                            \
-    hipLaunchKernelGGL((k_fused3bi<E, a, c, d>), g, b, 0, st, K);                                 \
-    return hipGetLastError();                                                                     \
-  }
-      NTT_FUSED_IP_CASE(6, 6, 6)
-      NTT_FUSED_IP_CASE(6, 7, 6)
-      NTT_FUSED_IP_CASE(7, 6, 7)
-#undef NTT_FUSED_IP_CASE
-      return hipErrorInvalidValue;
-    }
-#define NTT_FUSED_CASE(a, c, d)                                                                   \
-  if (r1 == a && r2 == c && r3 == d) {                                                            \
-    if (F.mode == 1) {                                                                            \
-      hipLaunchKernelGGL((k_fused3b<E, a, c, d>), g, b, 0, st, K);                                \
-      return hipGetLastError();                                                                   \
-    }                                                                                             \
-    hipLaunchKernelGGL((k_fused3<E, a, c, d>), g, b, 0, st, K);                                   \
-    return hipGetLastError();                                                                     \
-  }
-    NTT_FUSED_CASE(6, 6, 6)
-    NTT_FUSED_CASE(7, 6, 6)
-    NTT_FUSED_CASE(7, 7, 6)
-    NTT_FUSED_CASE(7, 7, 7)
-    NTT_FUSED_CASE(8, 7, 7)
-    NTT_FUSED_CASE(8, 8, 7)
-    NTT_FUSED_CASE(8, 8, 8)
-#undef NTT_FUSED_CASE
-    return hipErrorInvalidValue;
-  }
-}
-
-template <class E>
-hipError_t fused3_capacity(int r1, int r2, int r3, int device, uint32_t* wgs, uint32_t mode) {
-  if constexpr (!(E::FASTRED && E::SHOUP_OUTER && !E::LDS_TW && E::TILE_LOG == 10 && E::EPT == 4)) {
-    return hipErrorInvalidValue;
-  } else {
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return hipErrorInvalidValue;
-    const int threads = (1 << E::TILE_LOG) / E::EPT;
-    hipError_t e = hipErrorInvalidValue;
-#define NTT_FUSED_OCC(a, c, d)                                                                         \
-  if (r1 == a && r2 == c && r3 == d)                                                                   \
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(                                                   \
-        &per, mode == 1 ? reinterpret_cast<const void*>(&k_fused3b<E, a, c, d>)                        \
-                        : reinterpret_cast<const void*>(&k_fused3<E, a, c, d>),                        \
-        threads, 0);
-#define NTT_FUSED_IP_OCC(a, c, d)                                                                      \
-  if (mode == 2 && r1 == a && r2 == c && r3 == d)                                                      \
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(&k_fused3bi<E, a, c, d>), \
-                                                     threads, 0);
-    NTT_FUSED_IP_OCC(6, 6, 6)
-    NTT_FUSED_IP_OCC(6, 7, 6)
-    NTT_FUSED_IP_OCC(7, 6, 7)
-#undef NTT_FUSED_IP_OCC
-    if (mode != 2) {
-    NTT_FUSED_OCC(6, 6, 6)
-    NTT_FUSED_OCC(7, 6, 6)
-    NTT_FUSED_OCC(7, 7, 6)
-    NTT_FUSED_OCC(7, 7, 7)
-    NTT_FUSED_OCC(8, 7, 7)
-    NTT_FUSED_OCC(8, 8, 7)
-    NTT_FUSED_OCC(8, 8, 8)
-    }
-#undef NTT_FUSED_OCC
-    if (e != hipSuccess) return e;
-    *wgs = (uint32_t)(cus * per);
-    return hipSuccess;
-  }
+  const auto k = final_ipn_kernel<E>(logr);
+  if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(k),
+                                                         (1 << tile_log_of<E>()) / E::EPT, 0) != hipSuccess)
+    return 0;
+  return (per > 0 && cus > 0) ? (uint32_t)per * (uint32_t)cus : 0u;
 }
 
 // Element-wise kernels run as grid-stride loops over at most 2^20 workgroups of 256 threads:
@@ -2323,20 +1874,7 @@ static hipError_t launch_pass_r(const uint32_t* src, uint32_t* dst, const PassAr
 template <class E, int KIND>
 hipError_t launch_pass_kind(int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
                                 uint32_t batch, hipStream_t st) {
-  switch (logr) {
-    case 3: return launch_pass_r<E, KIND, 3>(src, dst, A, grid, batch, st);
-    case 4: return launch_pass_r<E, KIND, 4>(src, dst, A, grid, batch, st);
-    case 5: return launch_pass_r<E, KIND, 5>(src, dst, A, grid, batch, st);
-    case 6: return launch_pass_r<E, KIND, 6>(src, dst, A, grid, batch, st);
-    case 7: return launch_pass_r<E, KIND, 7>(src, dst, A, grid, batch, st);
-    case 8: return launch_pass_r<E, KIND, 8>(src, dst, A, grid, batch, st);
-    case 9: return launch_pass_r<E, KIND, 9>(src, dst, A, grid, batch, st);
-    case 10: return launch_pass_r<E, KIND, 10>(src, dst, A, grid, batch, st);
-    case 11: return launch_pass_r<E, KIND, 11>(src, dst, A, grid, batch, st);
-    case 12: return launch_pass_r<E, KIND, 12>(src, dst, A, grid, batch, st);
-    case 13: return launch_pass_r<E, KIND, 13>(src, dst, A, grid, batch, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_radix<3, 13>(logr, [&](auto R) { return launch_pass_r<E, KIND, R>(src, dst, A, grid, batch, st); });
 }
 
 template <class E>
@@ -2400,20 +1938,7 @@ static hipError_t launch_lde_r(const uint32_t* src, uint32_t* dst, const PassArg
 template <class E, int KIND>
 static hipError_t launch_lde_kind(int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
                                   uint32_t batch, hipStream_t st) {
-  switch (logr) {
-    case 3: return launch_lde_r<E, KIND, 3>(src, dst, A, grid, batch, st);
-    case 4: return launch_lde_r<E, KIND, 4>(src, dst, A, grid, batch, st);
-    case 5: return launch_lde_r<E, KIND, 5>(src, dst, A, grid, batch, st);
-    case 6: return launch_lde_r<E, KIND, 6>(src, dst, A, grid, batch, st);
-    case 7: return launch_lde_r<E, KIND, 7>(src, dst, A, grid, batch, st);
-    case 8: return launch_lde_r<E, KIND, 8>(src, dst, A, grid, batch, st);
-    case 9: return launch_lde_r<E, KIND, 9>(src, dst, A, grid, batch, st);
-    case 10: return launch_lde_r<E, KIND, 10>(src, dst, A, grid, batch, st);
-    case 11: return launch_lde_r<E, KIND, 11>(src, dst, A, grid, batch, st);
-    case 12: return launch_lde_r<E, KIND, 12>(src, dst, A, grid, batch, st);
-    case 13: return launch_lde_r<E, KIND, 13>(src, dst, A, grid, batch, st);
-    default: return hipErrorInvalidValue;
-  }
+  return with_radix<3, 13>(logr, [&](auto R) { return launch_lde_r<E, KIND, R>(src, dst, A, grid, batch, st); });
 }
 
 // The inputs of a low-degree extension times c^j, into a staging buffer of the same layout
@@ -2451,152 +1976,6 @@ hipError_t launch_lde_pass(int kind, int logr, const uint32_t* src, uint32_t* ds
   if (kind == KIND_COLUMN) return launch_lde_kind<E, KIND_COLUMN>(logr, src, dst, A, grid, batch, st);
   if (kind == KIND_SINGLE) return launch_lde_kind<E, KIND_SINGLE>(logr, src, dst, A, grid, batch, st);
   return hipErrorInvalidValue;
-}
-
-// ---------------------------------------------------------------------------- row-major matrix passes
-// One pass over the columns of a row-major matrix (pass_tile's strip form, MAT): workgroup g runs strip
-// g mod A.mat_ns of tile g / A.mat_ns, so the strips of one tile -- which share the lines that a row
-// boundary or a strip boundary cuts -- are dispatched together.  One scalar division per workgroup.
-template <class E, int LOGR, int KIND, int PRO>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_pass_mat(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const PassArgs<E> A) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[pass_lds_words<E, LOGR, KIND>()];
-  __shared__ __attribute__((aligned(16))) uint32_t lds_tw[pass_ltw<E, KIND, false>() ? (1 << LOGR) * E::TW : 1];
-  const uint32_t w = blockIdx.x / A.mat_ns, strip = blockIdx.x - w * A.mat_ns;
-  pass_tile<E, LOGR, KIND, false, false, PRO, true, 1, false, false, false, 0, true>(src, dst, A, w, strip, lds, lds_tw);
-}
-
-template <class E, int LOGR>
-static hipError_t launch_mat_r(int kind, bool lde, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A,
-                               uint32_t grid, hipStream_t st) {
-  if constexpr (!HasMat<E>::value || LOGR > mat_max_radix_log<E>()) {
-    return hipErrorInvalidValue;
-  } else {
-    static_assert(!E::FASTRED && lde_mul_at_load<E, KIND_COLUMN>(), "matrix engines");
-    const dim3 g(grid), b((1 << E::TILE_LOG) / E::EPT);
-    // the strip is no wider than the tile's columns (column pass) or blocks (final pass), and no narrower
-    // than the 64-byte rule allows
-    if (A.mat_w == 0 || A.mat_ns == 0 || A.il + LOGR > (uint32_t)E::TILE_LOG || A.fs || A.tw_epi || A.src2 ||
-        A.tw_full || A.tw_sh)
-      return hipErrorInvalidValue;
-    // the row maps reverse log_n bits of a 32-bit row; the epilogue needs both of its tables, and is the
-    // only use of tw_in outside the PRO_LDE pass
-    if (A.log_n < (uint32_t)LOGR || A.log_n > 31 || (A.mat_ops & ~(MAT_REV_IN | MAT_REV_OUT | MAT_MUL_OUT)))
-      return hipErrorInvalidValue;
-    const bool mul_out = (A.mat_ops & MAT_MUL_OUT) != 0;
-    if (mul_out && (lde || !A.tw_in || !A.tw_in_hi)) return hipErrorInvalidValue;
-    if (kind == KIND_COLUMN && lde) {
-      if (A.src_stride == 0 || (A.mat_ops & MAT_REV_IN)) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_COLUMN, PRO_LDE>), g, b, 0, st, src, dst, A);
-    } else if (lde || (A.tw_in && !mul_out)) {
-      return hipErrorInvalidValue;
-    } else if (kind == KIND_COLUMN) {
-      hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_COLUMN, PRO_NONE>), g, b, 0, st, src, dst, A);
-    } else if (kind == KIND_FINAL) {
-      hipLaunchKernelGGL((k_pass_mat<E, LOGR, KIND_FINAL, PRO_NONE>), g, b, 0, st, src, dst, A);
-    } else {
-      return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-}
-
-template <class E>
-hipError_t launch_mat_pass(int kind, int logr, bool lde, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A,
-                           uint32_t grid, hipStream_t st) {
-  switch (logr) {
-    case 3: return launch_mat_r<E, 3>(kind, lde, src, dst, A, grid, st);
-    case 4: return launch_mat_r<E, 4>(kind, lde, src, dst, A, grid, st);
-    case 5: return launch_mat_r<E, 5>(kind, lde, src, dst, A, grid, st);
-    case 6: return launch_mat_r<E, 6>(kind, lde, src, dst, A, grid, st);
-    case 7: return launch_mat_r<E, 7>(kind, lde, src, dst, A, grid, st);
-    case 8: return launch_mat_r<E, 8>(kind, lde, src, dst, A, grid, st);
-    case 9: return launch_mat_r<E, 9>(kind, lde, src, dst, A, grid, st);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// Matrix transforms of 2 and 4 rows: a thread per column holds the column's inputs in registers (so
-// src may be dst) and forms the n outputs as k_dft_naive does.
-template <class E>
-__global__ void k_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E> A, uint32_t n_in) {
-  const uint32_t n = 1u << A.log_n;
-  const bool mul_out = (A.mat_ops & MAT_MUL_OUT) != 0;
-  // the row maps (MAT_REV_IN / MAT_REV_OUT): log_n is 1 or 2 here
-  auto row_of = [&](uint32_t r, uint32_t bit) -> uint32_t {
-    return (A.mat_ops & bit) ? __builtin_bitreverse32(r) >> (32 - A.log_n) : r;
-  };
-  // debug builds: an index outside its buffer is recorded and redirected to element 0
-  auto ck = [&](size_t i, [[maybe_unused]] size_t lim) -> size_t {
-#if NTT_DEBUG_CHECKS
-    if (i >= lim) {
-      ntt_dbg_flag(A.F.dbg, NTT_DBG_BOUNDS);
-      return 0;
-    }
-#endif
-    return i;
-  };
-  NTT_GRID_STRIDE(b, A.mat_w) {
-    uint32_t x[4][E::W];
-    static_for<4>([&](auto J) {
-      constexpr int j = J;
-      if (j < n_in) {
-        E::load(x[j], src, ck((size_t)row_of(j, MAT_REV_IN) * A.mat_w + b, A.dbg_src_n));
-#if NTT_DEBUG_CHECKS
-        if (!E::dbg_canonical(x[j], A.F)) ntt_dbg_flag(A.F.dbg, NTT_DBG_INPUT);
-#endif
-        if (A.tw_in && !mul_out) {  // c^j from the shift's two-level tables
-          typename E::Tw tl, th;
-          E::tload(tl, A.tw_in, (uint32_t)(j & ((1u << A.lo_bits) - 1)));
-          E::tload(th, A.tw_in_hi, (uint32_t)(j >> A.lo_bits));
-          E::mul(tl.w, th, A.F);
-          E::mulv(x[j], tl.w, A.F);
-        }
-      }
-    });
-    static_for<4>([&](auto K) {
-      constexpr int k = K;
-      if (k < n) {
-        uint32_t acc[E::W], v[E::W];
-        typename E::Tw w;
-#pragma unroll
-        for (int l = 0; l < E::W; ++l) acc[l] = x[0][l];
-        E::tload(w, A.tw_int, 0);
-        E::mul(acc, w, A.F);
-        static_for<3>([&](auto J1) {
-          constexpr int j = J1 + 1;
-          if (j < n_in) {
-#pragma unroll
-            for (int l = 0; l < E::W; ++l) v[l] = x[j][l];
-            E::tload(w, A.tw_int, (j * k) & (n - 1));
-            E::mul(v, w, A.F);
-            E::template bfly_l<E::IN>(acc, v, A.F);  // acc <- acc + v (the difference is discarded)
-            E::template reduce<2 * E::IN, E::IN>(acc, A.F);
-          }
-        });
-        if (A.flags & 1u) E::mul(acc, A.F.ninv, A.F);
-        if (mul_out) {  // c^-k, the shift's inverse tables
-          typename E::Tw tl, th;
-          E::tload(tl, A.tw_in, (uint32_t)(k & ((1u << A.lo_bits) - 1)));
-          E::tload(th, A.tw_in_hi, (uint32_t)(k >> A.lo_bits));
-          E::mul(tl.w, th, A.F);
-          E::mulv(acc, tl.w, A.F);
-        }
-        E::template store<E::IN>(dst, ck((size_t)row_of(k, MAT_REV_OUT) * A.mat_w + b, A.dbg_dst_n), acc, A.F);
-      }
-    });
-  }
-}
-
-template <class E>
-hipError_t launch_mat_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t n_in, hipStream_t st) {
-  if constexpr (!HasMat<E>::value) {
-    return hipErrorInvalidValue;
-  } else {
-    if (A.log_n < 1 || A.log_n > 2 || n_in == 0 || n_in > (1u << A.log_n) || A.mat_w == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_mat_naive<E>), dim3(grid_1d(A.mat_w)), dim3(256), 0, st, src, dst, A, n_in);
-    return hipGetLastError();
-  }
 }
 
 template <class E>
@@ -2641,22 +2020,6 @@ hipError_t launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* c, s
                                          uint32_t, hipStream_t);                                             \
   template hipError_t launch_lde_scale<E>(const uint32_t*, uint32_t*, size_t, uint32_t, const uint32_t*,       \
                                           const uint32_t*, uint32_t, const typename E::Args&, hipStream_t);
-
-// The row-major matrix passes of one engine (a translation unit of their own: ntt_*_mat.hip)
-#define NTT_INSTANTIATE_MAT(E)                                                                                 \
-  template hipError_t launch_mat_pass<E>(int, int, bool, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
-                                         hipStream_t);                                                         \
-  template hipError_t launch_mat_naive<E>(const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, hipStream_t);
-
-#define NTT_INSTANTIATE_FUSED(E)                                                                                \
-  template hipError_t launch_fused3<E>(int, int, int, const uint32_t*, uint32_t*, uint32_t*, const PassArgs<E>&,     \
-                                       const PassArgs<E>&, const PassArgs<E>&, const FusedArgs&, hipStream_t);      \
-  template hipError_t fused3_capacity<E>(int, int, int, int, uint32_t*, uint32_t);
-
-#define NTT_INSTANTIATE_FUSED2(E)                                                                                 \
-  template hipError_t launch_fused2<E>(int, int, const uint32_t*, uint32_t*, uint32_t*, const PassArgs<E>&,           \
-                                       const PassArgs<E>&, const FusedArgs&, hipStream_t);                          \
-  template hipError_t fused2_capacity<E>(int, int, int, uint32_t*, uint32_t);
 
 #define NTT_INSTANTIATE(E)                                                                                         \
   NTT_EXTERN_KIND(E, KIND_COLUMN)                                                                                  \

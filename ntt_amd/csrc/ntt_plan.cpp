@@ -1130,7 +1130,7 @@ struct PlanImpl final : PlanBase {
   bool single_launch(const PassArgs<E>* PA, const uint32_t* in, uint32_t* work, uint32_t* out, bool inplace,
                      hipStream_t st, int& rc) {
     constexpr bool two = fused2_engine<E>();
-    if constexpr (!two && !std::is_same_v<E, Eng256>) {
+    if constexpr (!two && !fused3_engine<E>()) {
       return false;
     } else {
       if (!(two ? npass == 2 && fused2_ready(PA, inplace) : inplace ? fused_ip_ready(PA) : fused_ready(PA)))
@@ -1140,11 +1140,12 @@ struct PlanImpl final : PlanBase {
       if (two) F.trace = fused_trace_buffer(F.nwg);
       PassArgs<E> A1 = PA[0], B = PA[npass - 1];
       if (inplace) {  // every pass in the caller's buffer, no scratch
-        A1.ipn_go = F.sync + F.rbase;  // pass 1's stores wait for the residency decision (barrier 1)
+        constexpr FusedSync S = fused_sync_barriers(two ? FUSED2BI_BARRIERS : FUSED3BI_BARRIERS);
+        A1.ipn_go = F.sync + S.go(1);  // pass 1's stores wait for the residency decision (barrier 1)
         A1.wd = F.wd;
         B.flags &= ~2u;
         B.ipn_sync = F.sync;
-        B.ipn_go = F.sync + F.rbase + (two ? 64 : 96);  // the final pass's barrier (the third / fourth): its go word
+        B.ipn_go = F.sync + S.go(S.lines);  // the final pass's barrier (the form's last): its go word
         B.ipn_shards = F.shards;                        // its arrival shards (cumulative, like the top counter)
         B.wd = F.wd;
         in = out;
@@ -1322,7 +1323,7 @@ struct PlanImpl final : PlanBase {
     return PA[0].tw_full && PA[1].tw_full && PA[1].tw_sh && !PA[0].src2 && !PA[0].tw_in;
   }
 
-  // ---- k_fused3 (ntt_kernels_impl.hpp): 3-pass FAST 256-bit plans whose passes 1 and 2 take full tables
+  // ---- k_fused3 (ntt_fused_impl.hpp): 3-pass FAST 256-bit plans whose passes 1 and 2 take full tables
   // and whose radices the fused kernel is instantiated for
   DevBuf d_sync;  // FusedArgs::sync words
   FusedArgs fargs{};
@@ -1331,50 +1332,38 @@ struct PlanImpl final : PlanBase {
     return fused_state.ready([&] { return build_fused(); }) && fused3_passes_ok(PA);
   }
   bool build_fused() {
-    if constexpr (!std::is_same_v<E, Eng256>) {
+    if constexpr (!fused3_engine<E>()) {
       return false;
     } else {
       if (npass != 3 || !use_full || !d_full_sh || !full_sh_ok[1] || !Ff.red_ok || !alloc_watch()) return false;
-      const unsigned tl = tile_log_of<E>();
       const uint32_t mode = knob::fused_mode();  // 0: the dataflow form (per-tile hand-offs), 1: grid barriers
       uint32_t cap = 0;
       if (fused3_capacity<E>((int)r[0], (int)r[1], (int)r[2], device, &cap, mode) != hipSuccess || cap == 0) return false;
-      const unsigned r1 = r[0], r2 = r[1], r3 = r[2];
-      const unsigned lt1 = tl - r1, lt2 = tl - r2, lt3 = tl - r3, lu = lt1 > lt2 ? lt1 : lt2;
-      if (r3 < lu || r1 < lt3) return false;  // schedule_ok guarantees both; kept as the kernel's contract
+      const FusedGeom g = fused_geometry(tile_log_of<E>(), n, r[0], r[1], r[2], cap, mode);
+      if (!g.ok) return false;  // schedule_ok guarantees it; kept as the kernel's contract
+      fused_verbose("libntt: fused schedule mode %u", g.tiles, g.nwg, cap, mode);
+      if (!alloc_sync(d_sync, g.sync().total())) return false;
       FusedArgs F{};
-      F.tiles = (uint32_t)(n >> tl);
-      F.nwg = F.tiles < cap ? F.tiles : cap;
-      F.k1_mask = (1u << (r3 - lt1)) - 1;
-      F.k1_shift = lu - lt1;
-      F.cg_log = r3 - lt2;
-      F.k2_shift = lu - lt2;
-      F.t3_log = lt3;
-      F.r2 = r2;
-      F.n12 = 1u << (r3 - lu);
-      F.n23 = 1u << (r1 - lt3);
-      F.need12 = 1u << (lu - lt1 + r2);
-      F.need23 = 1u << r2;
-      F.mode = mode;
-      fused_verbose("libntt: fused schedule mode %u", F.tiles, F.nwg, cap, mode);
-      F.dbg = knob::fused_dbg();
-      F.rbase = (4 + F.n12 + F.n23 + 31) & ~31u;
-      const size_t words = F.rbase + 32 * (F.n12 + F.n23);
-      // then the abort word and the 8 barrier shards, each on a line of its own
-      if (!alloc_sync(d_sync, words + 32 * 9)) return false;
       F.sync = d_sync.get();
-      F.wd.abort = F.sync + words;
-      F.shards = F.sync + words + 32;
+      F.tiles = g.tiles, F.nwg = g.nwg;
+      F.k1_mask = g.k1_mask, F.k1_shift = g.k1_shift;
+      F.cg_log = g.cg_log, F.k2_shift = g.k2_shift, F.t3_log = g.t3_log, F.r2 = g.r2;
+      F.n12 = g.n12, F.n23 = g.n23, F.need12 = g.need12, F.need23 = g.need23;
+      F.rbase = g.rbase;
+      F.dbg = knob::fused_dbg();
+      F.mode = g.mode;
+      F.wd.abort = F.sync + g.sync().abort_word();
+      F.shards = F.sync + g.sync().shards();
       fargs = F;
       return true;
     }
   }
 
   // ---- the two-pass single launch on 4096-element tiles (2^20 4-limb plans: k_fused2b, and k_fused2bi
-  // in place; ntt_kernels_impl.hpp).  Plain launches of at most the occupancy query's workgroups; the
+  // in place; ntt_fused_impl.hpp).  Plain launches of at most the occupancy query's workgroups; the
   // in-place form needs every one of the 256 final tiles resident.
-  // Sync words: [0] top arrivals, [1] exits; go words at 32, 64, 96 (in place: residency, pass barrier,
-  // final barrier); abort at 128; shards at 160 + 32 s.
+  // Sync words: both forms share the in-place form's (FUSED2BI_BARRIERS go words: residency, pass barrier,
+  // final barrier; k_fused2b uses the first), FusedSync in plan_fused.hpp.
   DevBuf d_sync2;
   FusedArgs fargs2{}, fargs2_ip{};
   Lazy fused2_state[2];  // [in place]
@@ -1393,15 +1382,16 @@ struct PlanImpl final : PlanBase {
       uint32_t cap = 0;
       if (fused2_capacity<E>((int)r[0], (int)r[1], device, &cap, mode) != hipSuccess || cap == 0) return false;
       if (inplace && cap < tiles) return false;
-      if (!d_sync2 && !alloc_sync(d_sync2, 416)) return false;
+      constexpr FusedSync S = fused_sync_barriers(FUSED2BI_BARRIERS);
+      if (!d_sync2 && !alloc_sync(d_sync2, S.total())) return false;
       FusedArgs F{};
       F.tiles = tiles;
       F.nwg = inplace ? tiles : (tiles < cap ? tiles : cap);
       F.mode = mode;
-      F.rbase = 32;
+      F.rbase = S.rbase;
       F.sync = d_sync2.get();
-      F.wd.abort = F.sync + 128;
-      F.shards = F.sync + 160;
+      F.wd.abort = F.sync + S.abort_word();
+      F.shards = F.sync + S.shards();
       fused_verbose("libntt: two-pass single launch (mode %u)", tiles, F.nwg, cap, mode);
       (inplace ? fargs2_ip : fargs2) = F;
       return true;
@@ -1435,14 +1425,14 @@ struct PlanImpl final : PlanBase {
 
   // ---- the in-place single launch (NTT_PLAN_SINGLE_LAUNCH on an NTT_PLAN_IN_PLACE plan, k_fused3bi):
   // 3-pass palindromic FAST 256-bit schedules whose tiles all fit the device at once (2^18 .. 2^20)
-  DevBuf d_sync_ip;  // [0] top arrivals, [1] exits; go words at 32 (residency), 64, 96, 128; abort at 160; shards at 192 + 32 s
+  DevBuf d_sync_ip;  // FusedSync of FUSED3BI_BARRIERS barriers: go words for residency and the three grid barriers
   FusedArgs fargs_ip{};
   Lazy fused_ip_state;
   bool fused_ip_ready(const PassArgs<E>* PA) {
     return fused_ip_state.ready([&] { return build_fused_ip(); }) && fused3_passes_ok(PA);
   }
   bool build_fused_ip() {
-    if constexpr (!std::is_same_v<E, Eng256>) {
+    if constexpr (!fused3_engine<E>()) {
       return false;
     } else {
       if (npass != 3 || r[0] != r[2] || !use_full || !d_full_sh || !full_sh_ok[1] || !Ff.red_ok) return false;
@@ -1453,12 +1443,13 @@ struct PlanImpl final : PlanBase {
       FusedArgs F{};
       F.tiles = F.nwg = tiles;
       F.mode = 2;
-      F.rbase = 32;
+      constexpr FusedSync S = fused_sync_barriers(FUSED3BI_BARRIERS);
+      F.rbase = S.rbase;
       fused_verbose("libntt: in-place single launch", tiles, tiles, cap);
-      if (!alloc_sync(d_sync_ip, 448)) return false;
+      if (!alloc_sync(d_sync_ip, S.total())) return false;
       F.sync = d_sync_ip.get();
-      F.wd.abort = F.sync + 160;
-      F.shards = F.sync + 192;
+      F.wd.abort = F.sync + S.abort_word();
+      F.shards = F.sync + S.shards();
       fargs_ip = F;
       return true;
     }
