@@ -32,8 +32,7 @@
 #include "plan_devmem.hpp"    // the plan's own parts, included here alone: DevBuf, Lazy, the watchdog-word pool
 #include "plan_hostmath.hpp"  // HostField, EngHost<E>
 #include "plan_knobs.hpp"     // every environment variable, as knob::name()
-#include "plan_rivals.hpp"    // Rivals<E, Plan>: the rival schedules
-#include "plan_schedule.hpp"  // schedule_for, schedule_palindrome
+#include "plan_schedule.hpp"  // schedule_for, schedule_palindrome, mid_digits, overlaps
 
 using namespace ntt;
 
@@ -41,18 +40,61 @@ namespace {
 
 thread_local int g_last_error = NTT_OK;
 
-// A low-degree extension through run_io (PlanImpl::lde): the inputs' length and, where the shift is
-// not folded into the first pass's outer table, its two-level tables (null: no shift)
-struct LdeIO {
+// What the first pass of a transform reads and multiplies by (run_io).  Every route that exists has a
+// named constructor; a call site names its route.
+struct FirstPass {
+  const uint32_t* src2 = nullptr;   // second operand: the pass starts from the product in * src2
+  const uint32_t* outer = nullptr;  // outer-twiddle table (w R_e, element format) that replaces the plan's own
+  // factors applied at load: one table (u^d, the fused coset; hi null) or a two-level pair (lo scaled by R_e, hi)
+  const uint32_t* at_load = nullptr;
+  const uint32_t* at_load_hi = nullptr;
+  // nonzero: the pass is the low-degree extension's (PRO_LDE), which reads n_in <= n inputs per transform
+  // and takes the padding from registers.  Without a table of its own it computes its outer twiddles
+  // from the plan's two-level tables.
   size_t n_in = 0;
-  const uint32_t* lo = nullptr;
-  const uint32_t* hi = nullptr;
-  // the engines without the product at load: the inputs are first scaled into `stage` (launch_lde_scale
-  // with these two-level tables), which the first pass then reads
+  // staging: the inputs are first scaled by the two-level pair into `stage` (one launch, recorded
+  // unlabelled), which the pass then reads
   const uint32_t* scale_lo = nullptr;
   const uint32_t* scale_hi = nullptr;
   uint32_t* stage = nullptr;
+
+  static FirstPass plain() { return {}; }
+  static FirstPass make(const uint32_t* src2, const uint32_t* outer, const uint32_t* lo, const uint32_t* hi, size_t n_in) {
+    FirstPass f;
+    f.src2 = src2, f.outer = outer, f.at_load = lo, f.at_load_hi = hi, f.n_in = n_in;
+    return f;
+  }
+  // fused polymul inverse: the product at load, the inverse's pass-1 table scaled by n^-1 R_e
+  static FirstPass product(const uint32_t* b, const uint32_t* outer_ninv) { return make(b, outer_ninv, nullptr, nullptr, 0); }
+  // fused coset forward: u^d at load, c^col folded into the outer table
+  static FirstPass coset(const uint32_t* outer_c, const uint32_t* u_pow) { return make(nullptr, outer_c, u_pow, nullptr, 0); }
+  // low-degree extension without a shift on the plan's own pass-1 table
+  static FirstPass lde_plan_table(size_t n_in, const uint32_t* plan_outer) { return make(nullptr, plan_outer, nullptr, nullptr, n_in); }
+  static FirstPass lde_coset(size_t n_in, const uint32_t* outer_c, const uint32_t* u_pow) {
+    return make(nullptr, outer_c, u_pow, nullptr, n_in);
+  }
+  // the shift's two-level factors at load (none: no shift), two-level outer twiddles
+  static FirstPass lde_at_load(size_t n_in, const uint32_t* lo = nullptr, const uint32_t* hi = nullptr) {
+    return make(nullptr, nullptr, lo, hi, n_in);
+  }
+  // the engines without the product at load: the shift's factors through the staging buffer
+  static FirstPass lde_staged(size_t n_in, const uint32_t* lo, const uint32_t* hi, uint32_t* stage) {
+    FirstPass f = lde_at_load(n_in);
+    f.scale_lo = lo, f.scale_hi = hi, f.stage = stage;
+    return f;
+  }
 };
+
+}  // namespace
+
+// the plan's features, each a struct the plan owns and hands a reference to itself; they name FirstPass
+#include "plan_fold.hpp"    // Fold<E, Plan>: ntt_fri_fold
+#include "plan_matrix.hpp"  // Matrix<E, Plan>: the row-major matrix transforms
+#include "plan_rivals.hpp"  // Rivals<E, Plan>: the rival schedules
+#include "plan_shift.hpp"   // Shift<E, Plan>: the shift cache, coset transforms, low-degree extension
+#include "plan_single.hpp"  // Single<E, Plan>: the single-launch schedules, the in-place final pass
+
+namespace {
 
 // ------------------------------------------------------------------------------ plan
 struct PlanBase {
@@ -207,23 +249,28 @@ struct PlanImpl final : PlanBase {
   size_t full_sh_off[2][8] = {};  // entry offsets into d_full_sh, [dir][pass]
   bool full_sh_ok[8] = {};         // pass i takes its outer twiddles from d_full_sh
   size_t off_pinvB = 0;           // p^-1 mod B (E::W limbs) in d_tab (Shoup-pair table build)
-  // table word offsets
-  size_t off_int_f[8] = {0}, off_int_i[8] = {0};
-  size_t off_lo_f = 0, off_hi_f = 0, off_lo_i = 0, off_hi_i = 0, off_hi_is = 0, off_r2 = 0;
-  size_t off_los_f = 0, off_los_i = 0;  // lo tables scaled by R_e (left factor of on-the-fly twiddles)
+  // table word offsets, [dir]: 0 forward, 1 inverse
+  size_t off_int[2][8] = {};
+  size_t off_los[2] = {}, off_hi[2] = {};  // los: the lo table scaled by R_e (left factor of on-the-fly twiddles)
+  size_t off_hi_is = 0, off_r2 = 0;                        // off_hi_is: the inverse's hi table scaled by n^-1
   size_t off_rm = 0;                    // R_e R^-1 (Montgomery-form pointwise product)
   size_t off_pow2inv = 0;               // 2^-k, k = 0..log_n, E::TW words each (build_fs_table's scale)
   size_t off_hi_ipm = 0;                // inverse hi table scaled by n^-1 R_e (fused polymul, pass 1)
   DevBuf d_full_pm;                     // inverse pass-1 outer twiddles x n^-1 R_e (fused polymul)
-  Rivals<E, PlanImpl> rivals{*this};    // the rival schedules' state and code (plan_rivals.hpp)
+  // the plan's features, each in a header of its own with a reference to the plan
+  Rivals<E, PlanImpl> rivals{*this};  // the rival schedules (plan_rivals.hpp)
+  Shift<E, PlanImpl> shift{*this};    // the shift cache, coset transforms, low-degree extension (plan_shift.hpp)
+  Matrix<E, PlanImpl> mat{*this};     // row-major matrix transforms (plan_matrix.hpp)
+  Fold<E, PlanImpl> folder{*this};    // FRI fold (plan_fold.hpp)
+  Single<E, PlanImpl> single{*this};  // single-launch schedules, the in-place final pass (plan_single.hpp)
   unsigned lo_bits = 0;
   uint32_t nrand = 1, top_bits = 28;
 
   // The two-level tables (lo scaled by R_e, hi) that the outer twiddles w_n^e of a direction are computed
   // from.  The inverse's hi table for pass 1 (index 0) carries n^-1; every other reader takes the plain one.
-  const uint32_t* outer_lo(int dir) const { return d_tab.get() + (dir ? off_los_i : off_los_f); }
+  const uint32_t* outer_lo(int dir) const { return d_tab.get() + off_los[dir]; }
   const uint32_t* outer_hi(int dir, unsigned pass) const {
-    return d_tab.get() + (dir ? (pass == 0 ? off_hi_is : off_hi_i) : off_hi_f);
+    return d_tab.get() + (dir && pass == 0 ? off_hi_is : off_hi[dir]);
   }
 
   // the members' buffers are freed after this body, with the plan's device current (~PlanBase)
@@ -258,12 +305,9 @@ struct PlanImpl final : PlanBase {
       H.r2 = x;
     }
     EH.init(H);  // needs r2 for to_mont
-    Vec<NH> pv, gv;
-    for (int i = 0; i < NH; ++i) {
-      pv[i] = p[i];
-      gv[i] = g[i];
-    }
-    if (!vec_lt<NH>(gv, pv)) return NTT_ERR_FIELD;
+    Vec<NH> gv;
+    for (int i = 0; i < NH; ++i) gv[i] = g[i];
+    if (!H.below_p(gv)) return NTT_ERR_FIELD;
     // (p - 1) >> log_n, and n | p - 1
     std::vector<uint32_t> pm1(p, p + NH);
     pm1[0] -= 1;  // p odd: no borrow
@@ -344,28 +388,21 @@ struct PlanImpl final : PlanBase {
     const Vec<NH> ninv_m = H.to_mont(ninv_c);
     for (int dir = 0; dir < 2; ++dir) {
       const Vec<NH>& wn = dir ? winv : w;
-      size_t* off_int = dir ? off_int_i : off_int_f;
       if (twiddle_only) {
         // no transform tables
       } else if (npass == 0) {
-        off_int[0] = push_powers(wn, n, nullptr);
+        off_int[dir][0] = push_powers(wn, n, nullptr);
       } else {
-        for (unsigned i = 0; i < npass; ++i) off_int[i] = push_powers(H.pow_u64(wn, n >> r[i]), 1ull << r[i], nullptr);
+        for (unsigned i = 0; i < npass; ++i)
+          off_int[dir][i] = push_powers(H.pow_u64(wn, n >> r[i]), 1ull << r[i], nullptr);
       }
       {  // two-level tables of w_n^e (outer twiddles, four-step twiddle_pack)
         lo_bits = (log_n + 1) / 2;
-        const size_t lo = push_powers(wn, 1ull << lo_bits, nullptr);
-        const size_t los = push_powers(wn, 1ull << lo_bits, nullptr, true);
+        (void)push_powers(wn, 1ull << lo_bits, nullptr);  // the plain lo table: no reader, kept for the table's layout
+        off_los[dir] = push_powers(wn, 1ull << lo_bits, nullptr, true);
         const Vec<NH> step = H.pow_u64(wn, 1ull << lo_bits);
-        const size_t hi = push_powers(step, 1ull << (log_n - lo_bits), nullptr);
-        if (dir == 0) {
-          off_lo_f = lo;
-          off_los_f = los;
-          off_hi_f = hi;
-        } else {
-          off_lo_i = lo;
-          off_los_i = los;
-          off_hi_i = hi;
+        off_hi[dir] = push_powers(step, 1ull << (log_n - lo_bits), nullptr);
+        if (dir == 1) {
           off_hi_is = push_powers(step, 1ull << (log_n - lo_bits), &ninv_m);
           // fused polymul: the pointwise Montgomery product leaves a b / R_e; fold R_e in here
           const Vec<NH> ninv_re_m = H.mul(ninv_m, H.to_mont(engine_radix_mod_p()));
@@ -557,14 +594,8 @@ struct PlanImpl final : PlanBase {
     return off;
   }
 
-  // ---- coset (low-degree extension): data[j] *= c^j before the forward, c^-j after the inverse
-  std::vector<uint32_t> coset_key;  // shift c (NH words) of the cached tables
-  DevBuf d_coset;
-  DevBuf d_coset_full;  // fused coset forward: pass-1 outer twiddles x c^col (n entries)
-  bool coset_full_ok = false;
-  size_t coset_off[2][3] = {};  // [dir][lo_s, hi, u^d (forward only)] word offsets into d_coset
-  DevBuf d_lde_stage;  // ntt_lde_batch: scaled inputs of the engines without the product at load
-  std::vector<uint32_t> pm2_;    // p - 2 (inversion exponent)
+  Vec<NH> wn_m[2];              // w_n, w_n^-1 (Montgomery form), for tables built after init
+  std::vector<uint32_t> pm2_;  // p - 2 (inversion exponent)
 
   DevBuf d_bad;  // canonical-range check counter
   int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) override {
@@ -583,396 +614,31 @@ struct PlanImpl final : PlanBase {
     return NTT_OK;
   }
 
-  // The cached c^j tables (d_coset) of `shift`: checked (canonical, nonzero) and rebuilt when it changed
-  int ensure_coset_tables(const uint64_t* shift, unsigned limbs64) {
-    Vec<NH> c{};
-    // (the host words may reach past the caller's limbs: Goldilocks, NH = 3 over one 64-bit limb)
-    for (int i = 0; i < NH && (unsigned)(i / 2) < limbs64; ++i) c[i] = (uint32_t)(shift[i / 2] >> (32 * (i % 2)));
-    for (unsigned i = (NH + 1) / 2; i < limbs64; ++i)
-      if (shift[i]) return NTT_ERR_ARG;
-    if ((NH & 1) && (unsigned)(NH / 2) < limbs64 && (shift[NH / 2] >> 32)) return NTT_ERR_ARG;
-    Vec<NH> pv;
-    for (int i = 0; i < NH; ++i) pv[i] = H.M.p[i];
-    if (!vec_lt<NH>(c, pv) || c == Vec<NH>{}) return NTT_ERR_ARG;
-    const std::vector<uint32_t> key(c.begin(), c.end());
-    if (key != coset_key) {
-      d_coset.reset();
-      coset_key.clear();
-      std::vector<uint32_t> host;
-      const Vec<NH> cm = H.to_mont(c);
-      const Vec<NH> cim = H.pow(cm, pm2_);
-      for (int dir = 0; dir < 2; ++dir) {
-        const Vec<NH>& b = dir ? cim : cm;
-        coset_off[dir][0] = push_powers_to(host, b, 1ull << lo_bits, nullptr, true);
-        const Vec<NH> step = H.pow_u64(b, 1ull << lo_bits);
-        coset_off[dir][1] = push_powers_to(host, step, 1ull << (log_n - lo_bits), nullptr, false);
-      }
-      // fused forward: u^d, u = c^s (s = n / R_1 columns of pass 1), d < R_1, Shoup entries
-      if (npass >= 2) coset_off[0][2] = push_powers_to(host, H.pow_u64(cm, n >> r[0]), 1ull << r[0], nullptr, false);
-      coset_full_ok = false;
-      if (!d_coset.alloc(host.size() * 4)) return NTT_ERR_HIP;
-      if (hipMemcpy(d_coset.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return NTT_ERR_HIP;
-      coset_key = key;
-    }
-    return NTT_OK;
+  // ---- the features' entry points (PlanBase), each in its part
+  int coset(void* d, const uint64_t* c, unsigned limbs64, bool inverse, hipStream_t st) override {
+    return shift.coset(d, c, limbs64, inverse, st);
   }
-
-  int coset(void* d, const uint64_t* shift, unsigned limbs64, bool inverse, hipStream_t st) override {
-    if (!d || !shift || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
-    if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
-    const int dir = inverse ? 1 : 0;
-    auto scale = [&]() {
-      return rc_of(launch_scale_pow<E>(static_cast<uint32_t*>(d), log_n, 1, d_coset.get() + coset_off[dir][0],
-                                       d_coset.get() + coset_off[dir][1], lo_bits, Ff, st));
-    };
-    if (!inverse) {
-      if (coset_fusable()) {  // the scale rides in pass 1: u^d at load, c^col in the outer twiddles
-        if (int rc = ensure_coset_full()) return rc;
-        uint32_t* x = static_cast<uint32_t*>(d);
-        return run_io(x, nullptr, x, 1, false, st, d_coset_full.get(), d_coset.get() + coset_off[0][2]);
-      }
-      if (int rc = scale()) return rc;
-      return run(d, 1, false, st);
-    }
-    if (int rc = run(d, 1, true, st)) return rc;
-    return scale();
-  }
-
-  // Low-degree extension: the first pass (PRO_LDE) reads the n_in = n >> log_blowup coefficients of
-  // each input and takes the padding from registers.  The shift's c^j is applied at that load: the
-  // fused coset's way (u^d at load, c^col in the cached outer table) where coset_fusable(), else from
-  // the shift's two-level tables where the pass has room (lde_mul_at_load), else by one launch over the
-  // inputs into the plan's staging buffer (recorded as an unlabelled launch).  Without a shift nothing
-  // of the shift cache is touched: a fusable plan's pass then takes the plan's own pass-1 table.
-  // The few passes without a PRO_LDE instance (lde_pass_available), 2- and 4-point plans, and fast-
-  // reduction plans that could not build their full tables go through lde_staged.
-  int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* shift, unsigned limbs64, unsigned batch,
+  int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* c, unsigned limbs64, unsigned batch,
           hipStream_t st) override {
-    if constexpr (!HasLde<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!in || !out || batch == 0 || log_blowup > log_n) return NTT_ERR_ARG;
-      if (flags & (NTT_PLAN_TWIDDLE_ONLY | NTT_PLAN_IN_PLACE)) return NTT_ERR_ARG;
-      const size_t n_in = (size_t)(n >> log_blowup), eb = (size_t)MEMW * 4;
-      const uintptr_t a0 = (uintptr_t)in, a1 = a0 + (size_t)batch * n_in * eb;
-      const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)batch * (size_t)n * eb;
-      if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // the first pass reads d_in while later tiles write d_out
-      if (shift)
-        if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
-      const uint32_t* src = static_cast<const uint32_t*>(in);
-      uint32_t* dst = static_cast<uint32_t*>(out);
-      if (log_n == 0) {  // one coefficient, one evaluation: c^0 = 1
-        if (hipMemcpyAsync(dst, src, (size_t)batch * eb, hipMemcpyDeviceToDevice, st) != hipSuccess) return NTT_ERR_HIP;
-        return NTT_OK;
-      }
-      const bool fastred = fast(Ff), fuse = coset_fusable();
-      const int kind = npass == 1 ? KIND_SINGLE : KIND_COLUMN;
-      if (npass == 0 || !lde_pass_available<E>(kind, (int)r[0], fastred) || (fastred && npass >= 2 && !fuse))
-        return lde_staged(src, dst, n_in, shift != nullptr, batch, st);
-      LdeIO L;
-      L.n_in = n_in;
-      if (fuse) {
-        if (!shift && !d_fulls[0]) return lde_staged(src, dst, n_in, false, batch, st);
-        if (!shift)  // the plan's own pass-1 table (element format), no product at load
-          return run_io(src, nullptr, dst, batch, false, st, d_fulls[0].get() + full_off[0] * TABW, nullptr, nullptr, &L);
-        if (int rc = ensure_coset_full()) return rc;
-        return run_io(src, nullptr, dst, batch, false, st, d_coset_full.get(), d_coset.get() + coset_off[0][2], nullptr, &L);
-      }
-      if (shift) {
-        const uint32_t* lo = d_coset.get() + coset_off[0][0];
-        const uint32_t* hi = d_coset.get() + coset_off[0][1];
-        const bool at_load = npass == 1 ? lde_mul_at_load<E, KIND_SINGLE>() : lde_mul_at_load<E, KIND_COLUMN>();
-        if (at_load) {
-          L.lo = lo;
-          L.hi = hi;
-        } else {
-          // the multi-limb engines' first pass has no room for the two table entries: one launch over
-          // the batch n_in inputs scales them into the plan's staging buffer, which the pass then reads
-          if (!d_lde_stage.grow((size_t)batch * n_in * eb)) return NTT_ERR_HIP;
-          L.scale_lo = lo;
-          L.scale_hi = hi;
-          L.stage = d_lde_stage.get();
-        }
-      }
-      return run_io(src, nullptr, dst, batch, false, st, nullptr, nullptr, nullptr, &L);
-    }
+    return shift.lde(in, out, log_blowup, c, limbs64, batch, st);
   }
-
-  // The zero-padded route of a low-degree extension, for the plans whose first pass has no PRO_LDE
-  // form: the padded vectors are staged in d_out (memset, strided copy), scaled by c^j there
-  // (k_scale_pow over the N-sized vectors) and transformed in place by the plan's plain forward.
-  int lde_staged(const uint32_t* src, uint32_t* dst, size_t n_in, bool shifted, unsigned batch, hipStream_t st) {
-    const size_t eb = (size_t)MEMW * 4;
-    if (hipMemsetAsync(dst, 0, (size_t)batch * (size_t)n * eb, st) != hipSuccess ||
-        hipMemcpy2DAsync(dst, (size_t)n * eb, src, n_in * eb, n_in * eb, batch, hipMemcpyDeviceToDevice, st) != hipSuccess)
-      return NTT_ERR_HIP;
-    if (shifted && launch_scale_pow<E>(dst, log_n, batch, d_coset.get() + coset_off[0][0], d_coset.get() + coset_off[0][1], lo_bits,
-                                       Ff, st) != hipSuccess)
-      return NTT_ERR_HIP;
-    return run_io(dst, nullptr, dst, batch, false, st);
-  }
-
-  // ---- row-major matrix transforms (ntt_forward_matrix / ntt_inverse_matrix / ntt_lde_matrix): the
-  // transforms run down the columns of a [n][width] matrix on a schedule of their own (plan_schedule.hpp
-  // schedule_matrix: radices up to TILE >> strip, a strip of columns per pass), every pass in the strip
-  // form of the pass tile (k_pass_mat).  Column passes take their outer twiddles from the plan's
-  // two-level tables; the w_R^e tables of the matrix radices are built at the first matrix call.
-  Vec<NH> wn_m[2];              // w_n, w_n^-1 (Montgomery form), for tables built after init
-  Lazy mat_state;               // ready: d_mat_tab holds the tables below
-  DevBuf d_mat_tab;
-  unsigned mat_r[8] = {0}, mat_p = 0;
-  size_t mat_int[2][8] = {};    // [dir][pass]: word offset of w_{R_i}^e (naive sizes: pass 0 = w_n^e, e < n)
-  bool build_mat() {
-    unsigned tb[8];
-    if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), 1, mat_r, tb, mat_p)) return false;
-    std::vector<uint32_t> host;
-    for (int dir = 0; dir < 2; ++dir) {
-      if (mat_p == 0) mat_int[dir][0] = push_powers_to(host, wn_m[dir], n, nullptr, false);
-      for (unsigned i = 0; i < mat_p; ++i)
-        mat_int[dir][i] = push_powers_to(host, H.pow_u64(wn_m[dir], n >> mat_r[i]), 1ull << mat_r[i], nullptr, false);
-    }
-    return d_mat_tab.alloc(host.size() * 4) &&
-           hipMemcpy(d_mat_tab.get(), host.data(), host.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+  int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
+             const uint64_t* c, unsigned limbs64, unsigned order, hipStream_t st) override {
+    return mat.run(in, out, width, inverse, is_lde, log_blowup, c, limbs64, order, st);
   }
   int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const override {
-    if constexpr (!HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      unsigned rr[8] = {0}, tb[8], p = 0;
-      if (width == 0 || ((uint64_t)n * width) >> 32 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
-      if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), width, rr, tb, p)) return NTT_ERR_ARG;
-      if (npasses) *npasses = p;
-      if (radix_log)
-        for (int i = 0; i < 8; ++i) radix_log[i] = rr[i];
-      return NTT_OK;
-    }
+    return mat.info(width, npasses, radix_log);
   }
-  // in: [n_in = n >> log_blowup][width] (is_lde) or the matrix itself (in == out); out: [n][width]
-  // The _ex forms change addresses and one product, never the schedule: a forward shift is the lde's
-  // product at the first pass's load (PRO_LDE with every row present: it loads what the plain pass loads,
-  // all of it ahead of the tile's first store, so a transform of one pass stays safe in place); an inverse
-  // shift is c^-j at the last pass's store; BITREV_IN permutes the rows the first pass loads, BITREV_OUT
-  // the rows the last pass stores.
-  int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
-             const uint64_t* shift, unsigned limbs64, unsigned order, hipStream_t st) override {
-    if constexpr (!HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!in || !out || width == 0 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
-      if (((uint64_t)n * width) >> 32) return NTT_ERR_ARG;  // element indices are 32-bit in places
-      if (is_lde && log_blowup > log_n) return NTT_ERR_ARG;
-      if (order & ~(inverse ? NTT_MATRIX_BITREV_IN : NTT_MATRIX_BITREV_OUT)) return NTT_ERR_ARG;
-      const size_t n_in = is_lde ? (size_t)(n >> log_blowup) : (size_t)n, eb = (size_t)MEMW * 4;
-      if (is_lde) {
-        const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * width * eb;
-        const uintptr_t b0 = (uintptr_t)out, b1 = b0 + (size_t)n * width * eb;
-        if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // the first pass reads d_in while later tiles write d_out
-      }
-      if (shift)
-        if (int rc = ensure_coset_tables(shift, limbs64)) return rc;
-      unsigned tb[8] = {0}, rr[8], p = 0;
-      if (!schedule_matrix(log_n, E::TILE_LOG, mat_min_strip_log<E>(), width, rr, tb, p)) return NTT_ERR_ARG;
-      if (!mat_state.ready([&] { return build_mat(); })) return NTT_ERR_HIP;
-      const uint32_t* src = static_cast<const uint32_t*>(in);
-      uint32_t* dst = static_cast<uint32_t*>(out);
-      if (log_n == 0) {  // one row: the transform of one point, c^0 = 1
-        if (dst != src && hipMemcpyAsync(dst, src, width * eb, hipMemcpyDeviceToDevice, st) != hipSuccess) return NTT_ERR_HIP;
-        return NTT_OK;
-      }
-      const int dir = inverse ? 1 : 0;
-      // forward: c^j at the first pass's load (the lde's pass, here maybe with n_in = n and in == out);
-      // inverse: c^-j at the last pass's store
-      const bool mul_in = !inverse && shift, mul_out = inverse && shift;
-      const bool pro_lde = is_lde || mul_in;
-      const unsigned last = mat_p == 0 ? 0 : mat_p - 1;
-      auto mat_args = [&](unsigned i) {
-        PassArgs<E> A = base_args(inverse);
-        A.tw_int = d_mat_tab.get() + mat_int[dir][i];
-        A.mat_w = width;
-        A.il = tb[i];
-        A.mat_ns = (uint32_t)(((uint64_t)width + (1u << tb[i]) - 1) >> tb[i]);
-        A.dbg_src_n = A.dbg_dst_n = (size_t)n * width;
-        if (i == 0 && pro_lde) {
-          A.src_stride = n_in * MEMW;
-          A.dbg_src_n = n_in * width;
-          if (mul_in) {
-            A.tw_in = d_coset.get() + coset_off[0][0];
-            A.tw_in_hi = d_coset.get() + coset_off[0][1];
-          }
-        }
-        if (i == 0 && (order & NTT_MATRIX_BITREV_IN)) A.mat_ops |= MAT_REV_IN;
-        if (i == last && (order & NTT_MATRIX_BITREV_OUT)) A.mat_ops |= MAT_REV_OUT;
-        if (i == last && mul_out) {
-          A.mat_ops |= MAT_MUL_OUT;
-          A.tw_in = d_coset.get() + coset_off[1][0];
-          A.tw_in_hi = d_coset.get() + coset_off[1][1];
-        }
-        return A;
-      };
-      hipError_t e = hipSuccess;
-      begin(st);
-      if (mat_p == 0) {
-        PassArgs<E> A = mat_args(0);
-        A.flags = inverse ? 1u : 0u;
-        e = launch_mat_naive<E>(src, dst, A, (uint32_t)n_in, st);
-        mark(st, "n");
-        return rc_of(e);
-      }
-      uint32_t* work = dst;
-      if (mat_p >= 2) {  // n width elements, not the next power of two
-        if (!d_scratch.grow((size_t)n * width * SCRW * 4)) return NTT_ERR_HIP;
-        work = d_scratch.get();
-      }
-      unsigned blk = log_n;
-      const unsigned ncol = mat_p == 1 ? 1 : mat_p - 1;  // column passes (a transform of one pass is one)
-      for (unsigned i = 0; i < ncol && e == hipSuccess; ++i) {
-        PassArgs<E> A = mat_args(i);
-        A.tw_lo = outer_lo(dir);
-        A.tw_hi = outer_hi(dir, i);  // the inverse's pass 1 carries n^-1
-        A.log_blk = blk + tb[i];
-        A.log_m = log_n - blk;
-        A.src_user = i == 0 ? 1u : 0u;
-        const uint32_t grid = (uint32_t)(((n << tb[i]) >> E::TILE_LOG) * A.mat_ns);
-        e = launch_mat_pass<E>(KIND_COLUMN, (int)mat_r[i], i == 0 && pro_lde, i == 0 ? src : work, work, A, grid, st);
-        mark(st, mat_p == 1 ? "s" : "c", mat_r[i]);
-        blk -= mat_r[i];
-      }
-      if (mat_p >= 2 && e == hipSuccess) {
-        const unsigned i = mat_p - 1;
-        PassArgs<E> A = mat_args(i);
-        A.r1 = mat_r[0];
-        A.nmid = mat_p - 2;
-        for (unsigned m = 0; m < A.nmid; ++m) {  // middle digits, least significant first (pass_args)
-          const unsigned idx = mat_p - 2 - m;
-          A.mid_bits[m] = mat_r[idx];
-          unsigned off = 0;
-          for (unsigned j = 1; j < idx; ++j) off += mat_r[j];
-          A.mid_off[m] = off;
-        }
-        const uint32_t grid = (uint32_t)(((n << tb[i]) >> E::TILE_LOG) * A.mat_ns);
-        e = launch_mat_pass<E>(KIND_FINAL, (int)mat_r[i], false, work, dst, A, grid, st);
-        mark(st, "f", mat_r[i]);
-      }
-      return rc_of(e);
-    }
-  }
-
-  // ---- FRI fold (ntt_fri_fold): one launch of k_fri_fold.  Every constant is computed here, on the host,
-  // per call -- c^-1 (one inversion), 2^-k, the 2^(k-1) twiddles zeta^-e, and beta^(2^s), W beta^(2^s) for
-  // the k stages -- and travels in the kernel arguments; x0^-1's variable part w_N^-rev(i') comes from the
-  // plan's own inverse two-level tables (lo scaled by R_e, the plain hi: not the one carrying n^-1) at
-  // stride 2^(log_n - log_rows).  Nothing is cached, so the coset tables of the other calls stay as they are.
-  // The data keep their form: with t R_e as the variable operand mulv(x, t R_e) = x t whatever form x has,
-  // and the other products are by constants, so a NTT_PLAN_MONTGOMERY_IO plan runs the same code.
   int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree, uint64_t ext_w,
-           const uint64_t* beta, const uint64_t* shift, hipStream_t st) override {
-    if constexpr (!HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!in || !out || !beta || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
-      if (log_arity < 1 || log_arity > 4 || log_arity > log_rows || log_rows > log_n) return NTT_ERR_ARG;
-      if (ext_degree != 1 && ext_degree != 2 && ext_degree != 4) return NTT_ERR_ARG;
-      const unsigned d = ext_degree, k = log_arity;
-      Vec<NH> pv;
-      for (int i = 0; i < NH; ++i) pv[i] = H.M.p[i];
-      // one host word -> a canonical element (false: not below p)
-      auto canon = [&](uint64_t v, Vec<NH>& o) {
-        o = Vec<NH>{};
-        o[0] = (uint32_t)v;
-        if constexpr (NH > 1) o[1] = (uint32_t)(v >> 32);
-        else if (v >> 32) return false;
-        return vec_lt<NH>(o, pv);
-      };
-      Vec<NH> wc{}, cc{}, bc[4];
-      if (d > 1 && (!canon(ext_w, wc) || wc == Vec<NH>{})) return NTT_ERR_ARG;
-      for (unsigned j = 0; j < d; ++j)
-        if (!canon(beta[j], bc[j])) return NTT_ERR_ARG;
-      if (shift && (!canon(*shift, cc) || cc == Vec<NH>{})) return NTT_ERR_ARG;
-      const size_t eb = (size_t)MEMW * 4, n_in = (size_t)1 << log_rows, n_out = n_in >> k;
-      {
-        const uintptr_t a0 = (uintptr_t)in, a1 = a0 + n_in * d * eb;
-        const uintptr_t b0 = (uintptr_t)out, b1 = b0 + n_out * d * eb;
-        if (a0 < b1 && b0 < a1) return NTT_ERR_ARG;  // other workgroups still read d_in
-      }
-      FoldArgs<E> A{};
-      A.F = Ff;
-      A.lo_s = d_tab.get() + off_los_i;
-      A.hi = d_tab.get() + off_hi_i;
-      A.lo_bits = lo_bits;
-      A.tab_shift = log_n - log_rows;
-      A.log_m = log_rows - k;
-      A.vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-      A.src_words = n_in * d * MEMW;
-      A.dst_words = n_out * d * MEMW;
-      auto tw = [&](const Vec<NH>& m, typename E::Tw& t) {  // Montgomery-form host value -> twiddle
-        uint32_t enc[TW];
-        EH.encode(H.from_mont(m), enc);
-        static_assert(sizeof(typename E::Tw) == TW * 4, "a twiddle is its table entry");
-        memcpy(&t, enc, sizeof t);
-      };
-      tw(shift ? H.pow(H.to_mont(cc), pm2_) : H.r1, A.cinv);
-      {
-        Vec<NH> two{};
-        two[0] = 2;
-        tw(H.pow_u64(H.pow(H.to_mont(two), pm2_), k), A.scale);
-      }
-      {
-        const Vec<NH> zi = H.pow_u64(wn_m[1], n >> k);  // zeta^-1 = w_n^-(n / 2^k)
-        Vec<NH> acc = H.r1;
-        for (unsigned e = 0; e < 8; ++e) {
-          tw(acc, A.zeta[e]);
-          acc = H.mul(acc, zi);
-        }
-      }
-      {
-        const Vec<NH> wm = d > 1 ? H.to_mont(wc) : H.r1;
-        Vec<NH> b[4] = {}, zero{};
-        for (unsigned j = 0; j < d; ++j) b[j] = H.to_mont(bc[j]);
-        for (unsigned s = 0; s < 4; ++s) {
-          for (unsigned j = 0; j < 4; ++j) {
-            tw(j < d ? b[j] : zero, A.beta[s][j]);
-            tw(j < d ? H.mul(b[j], wm) : zero, A.wbeta[s][j]);
-          }
-          // b <- b^2 in F_p[X]/(X^d - W)
-          Vec<NH> lo[4] = {}, hi[4] = {};
-          for (unsigned i = 0; i < d; ++i)
-            for (unsigned j = 0; j < d; ++j) {
-              Vec<NH>& acc = i + j < d ? lo[i + j] : hi[i + j - d];
-              acc = H.add(acc, H.mul(b[i], b[j]));
-            }
-          for (unsigned j = 0; j < d; ++j) b[j] = H.add(lo[j], H.mul(hi[j], wm));
-        }
-      }
-      const int want = knob::fold_staged();
-      const bool staged = want < 0 ? kFoldStagedDefault : want != 0;
-      begin(st);
-      const hipError_t e = launch_fri_fold<E>(k, d, staged, static_cast<const uint32_t*>(in), static_cast<uint32_t*>(out), A, st);
-      mark(st, "x", k);
-      return rc_of(e);
-    }
+           const uint64_t* beta, const uint64_t* c, hipStream_t st) override {
+    return folder.run(in, out, log_rows, log_arity, ext_degree, ext_w, beta, c, st);
   }
-  // the load form of k_fri_fold without the knob: each thread loads its own fibre.  Measured faster than the
-  // form through LDS in five of six cases at 2^22 rows: the kernel is bound by its
-  // arithmetic, not by the lines its loads touch, and the staging costs occupancy
-  static constexpr bool kFoldStagedDefault = false;
+  bool single_launch_ready() override { return single.ready(); }
 
   // the engine's fast (quotient-estimate) reduction holds for this modulus in direction F
   static bool fast(const typename E::Args& F) {
     if constexpr (E::FASTRED) return F.red_ok != 0;
     else return false;
-  }
-  bool coset_fusable() const { return use_full && npass >= 2 && fast(Ff); }
-  // Pass-1 outer-twiddle table of the fused coset forward for the cached shift c: entry (col, k) =
-  // w_n^(col k) c^col R_e, layout of d_full (built on the device once per shift).
-  int ensure_coset_full() {
-    if (coset_full_ok) return NTT_OK;
-    if (!d_coset_full && !d_coset_full.alloc((size_t)n * TABW * 4)) return NTT_ERR_HIP;
-    if (launch_build_tw<E>(d_coset_full.get(), n, r[0], tile_log_of<E>() - r[0], 0, outer_lo(0), outer_hi(0, 0), lo_bits,
-                           Ff, nullptr, d_coset.get() + coset_off[0][0], d_coset.get() + coset_off[0][1]) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess)
-      return NTT_ERR_HIP;
-    coset_full_ok = true;
-    return NTT_OK;
   }
 
   // canonical value of the engine's Montgomery radix R_e mod p
@@ -1034,21 +700,37 @@ struct PlanImpl final : PlanBase {
   int run(void* d, unsigned batch, bool inverse, hipStream_t st) override {
     if (!d || batch == 0 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
     if (int rc = NTT_OK; !inverse && batch == 1 && rivals.run(static_cast<uint32_t*>(d), st, rc)) return rc;
-    return run_io(static_cast<uint32_t*>(d), nullptr, static_cast<uint32_t*>(d), batch, inverse, st);
+    return run_io(static_cast<uint32_t*>(d), static_cast<uint32_t*>(d), batch, inverse, st, FirstPass::plain());
+  }
+
+  // The first pass's arguments from its descriptor, for a column pass (PA[0] of pass_args) and for the
+  // one pass of a single-tile transform alike (which has no outer twiddles: tw_full is unused there).
+  // A table of the descriptor's own replaces the plan's; the low-degree extension's pass without one
+  // falls back to the two-level tables, never to the plan's table or its Shoup pairs.
+  void apply_first_pass(PassArgs<E>& A, const FirstPass& fp) const {
+    A.src2 = fp.src2;
+    A.tw_in = fp.at_load;
+    A.tw_in_hi = fp.at_load_hi;
+    if (fp.outer || fp.n_in) {
+      A.tw_full = fp.outer;
+      A.tw_sh = 0;
+    }
+    if (fp.n_in) {
+      A.src_stride = fp.n_in * MEMW;
+      A.dbg_src_n = fp.n_in;
+    }
   }
 
   // The arguments of a multi-pass transform's launches: column passes 0..npass-2, then the final pass
   // (PA[npass - 1]).  The parameters are run_io's.
-  void pass_args(PassArgs<E>* PA, bool inverse, bool inplace, uint32_t il, const uint32_t* in2, const uint32_t* full0,
-                 const uint32_t* tw_in, const FsIO* io, const LdeIO* lde) const {
+  void pass_args(PassArgs<E>* PA, bool inverse, bool inplace, uint32_t il, const FirstPass& fp, const FsIO* io) const {
     const int dir = inverse ? 1 : 0;
-    const size_t* off_int = inverse ? off_int_i : off_int_f;
     const bool full_dir = use_full && d_fulls[dir];  // else: the two-level tables
     unsigned blk = log_n;
     for (unsigned i = 0; i + 1 < npass; ++i) {
       PassArgs<E>& A = PA[i];
       A = base_args(inverse);
-      A.tw_int = d_tab.get() + off_int[i];
+      A.tw_int = d_tab.get() + off_int[dir][i];
       A.tw_lo = outer_lo(dir);
       A.tw_hi = outer_hi(dir, i);
       // pass 1 of a memory-bound engine (8-B P path) computes its outer twiddles from the
@@ -1060,28 +742,6 @@ struct PlanImpl final : PlanBase {
         A.tw_full = d_full_sh.get() + full_sh_off[dir][i] * TW;
         A.tw_sh = 1;
       }
-      if (i == 0 && in2) {  // the fused prologues bring their own pass-1 tables (w R_e)
-        A.src2 = in2;
-        A.tw_full = d_full_pm.get();
-        A.tw_sh = 0;
-      }
-      if (i == 0 && tw_in) {
-        A.tw_in = tw_in;
-        A.tw_full = full0;
-        A.tw_sh = 0;
-      }
-      if (i == 0 && lde) {  // PRO_LDE: short inputs; without the fused table, two-level outer twiddles
-        A.src_stride = lde->n_in * MEMW;
-        if (full0) {  // the shift's cached table with tw_in, or the plan's own pass-1 table without
-          A.tw_full = full0;
-          A.tw_sh = 0;
-        } else {
-          A.tw_full = nullptr;
-          A.tw_sh = 0;
-          A.tw_in = lde->lo;
-          A.tw_in_hi = lde->hi;
-        }
-      }
       A.log_blk = blk + il;
       A.log_m = log_n - blk;
       A.src_user = (i == 0) ? 1u : 0u;
@@ -1090,22 +750,15 @@ struct PlanImpl final : PlanBase {
     }
     PassArgs<E>& A = PA[npass - 1];
     A = base_args(inverse);
-    A.tw_int = d_tab.get() + off_int[npass - 1];
+    A.tw_int = d_tab.get() + off_int[dir][npass - 1];
     A.r1 = r[0];
     A.nmid = npass - 2;
-    // middle digits k_2..k_{p-1}, least significant (k_{p-1}) first
-    for (unsigned m = 0; m < A.nmid; ++m) {
-      const unsigned idx = npass - 2 - m;  // pass index (0-based) of digit k_{idx+1}
-      A.mid_bits[m] = r[idx];
-      unsigned off = 0;
-      for (unsigned j = 1; j < idx; ++j) off += r[j];
-      A.mid_off[m] = off;
-    }
+    mid_digits(r, npass, A.mid_bits, A.mid_off);
     set_fs(A, io, il, FS_MAP_OUT);
     if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
     if (inplace) A.flags |= 2u;
     for (unsigned i = 0; i < npass; ++i) set_extents(PA[i], io, il);
-    if (lde) PA[0].dbg_src_n = lde->n_in;
+    apply_first_pass(PA[0], fp);
     // XCD-grouped tile order (k_pass flag bit 2) for the column passes after the first whose runs are
     // shorter than a 128-B line (the 8-B path's 4-B scratch at radix 512: 64-B runs), so that the
     // two tiles sharing each line meet on one XCD's L2.  Passes of one column per tile (radix 4096 on
@@ -1123,55 +776,10 @@ struct PlanImpl final : PlanBase {
       }
   }
 
-  // The whole batch-1 transform as ONE launch, where the plan has such a schedule (NTT_PLAN_SINGLE_LAUNCH;
-  // built on first use) and these passes fit it: true when it was launched, rc its status.  Two passes
-  // on the 4096-element tiles (k_fused2b, in place k_fused2bi), else three on Eng256 (k_fused3 / k_fused3b,
-  // in place k_fused3bi).
-  bool single_launch(const PassArgs<E>* PA, const uint32_t* in, uint32_t* work, uint32_t* out, bool inplace,
-                     hipStream_t st, int& rc) {
-    constexpr bool two = fused2_engine<E>();
-    if constexpr (!two && !fused3_engine<E>()) {
-      return false;
-    } else {
-      if (!(two ? npass == 2 && fused2_ready(PA, inplace) : inplace ? fused_ip_ready(PA) : fused_ready(PA)))
-        return false;
-      FusedArgs F = two ? (inplace ? fargs2_ip : fargs2) : (inplace ? fargs_ip : fargs);
-      F.wd = watchdog(F.wd.abort);
-      if (two) F.trace = fused_trace_buffer(F.nwg);
-      PassArgs<E> A1 = PA[0], B = PA[npass - 1];
-      if (inplace) {  // every pass in the caller's buffer, no scratch
-        constexpr FusedSync S = fused_sync_barriers(two ? FUSED2BI_BARRIERS : FUSED3BI_BARRIERS);
-        A1.ipn_go = F.sync + S.go(1);  // pass 1's stores wait for the residency decision (barrier 1)
-        A1.wd = F.wd;
-        B.flags &= ~2u;
-        B.ipn_sync = F.sync;
-        B.ipn_go = F.sync + S.go(S.lines);  // the final pass's barrier (the form's last): its go word
-        B.ipn_shards = F.shards;                        // its arrival shards (cumulative, like the top counter)
-        B.wd = F.wd;
-        in = out;
-        work = nullptr;
-      }
-      hipError_t e;
-      {
-        FusedSerial order(device, st);
-        if constexpr (two) e = launch_fused2<E>((int)r[0], (int)r[1], in, work, out, A1, B, F, st);
-        else e = launch_fused3<E>((int)r[0], (int)r[1], (int)r[2], in, work, out, A1, PA[1], B, F, st);
-        order.done(e);
-      }
-      mark(st, "b");
-      if (F.trace && e == hipSuccess) dump_fused_trace(F, inplace, st);
-      rc = e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
-      return true;
-    }
-  }
-
-  // One transform (or a batch): reads `in` (and, for a fused polymul inverse, `in2`: the first pass
-  // starts from the pointwise product in * in2), writes `out` (may equal `in`).
-  // Fused coset forward: full0 replaces the first pass's outer-twiddle table and tw_in scales its
-  // inputs (PRO_COSET in ntt_kernels_impl.hpp).
-  int run_io(const uint32_t* in, const uint32_t* in2, uint32_t* out, unsigned batch, bool inverse, hipStream_t st,
-             const uint32_t* full0 = nullptr, const uint32_t* tw_in = nullptr, const FsIO* io = nullptr,
-             const LdeIO* lde = nullptr) {
+  // One transform (or a batch): reads `in`, writes `out` (may equal `in`); `fp` says what the first pass
+  // reads besides and multiplies by (FirstPass), `io` is a four-step piece's interface (the rank plan's).
+  int run_io(const uint32_t* in, uint32_t* out, unsigned batch, bool inverse, hipStream_t st, const FirstPass& fp,
+             const FsIO* io = nullptr) {
     const uint32_t il = (io && (io->fs & FS_IL)) ? io->il : 0u;
     if (io && (log_n == 0 || npass == 0)) return NTT_ERR_ARG;  // four-step pieces are >= 8 points
     if (log_n == 0) {
@@ -1179,43 +787,37 @@ struct PlanImpl final : PlanBase {
         return NTT_ERR_HIP;
       return NTT_OK;
     }
-    const size_t* off_int = inverse ? off_int_i : off_int_f;
+    const int dir = inverse ? 1 : 0;
+    const bool lde = fp.n_in != 0;
     hipError_t e = hipSuccess;
     begin(st);
-    if (lde && lde->stage) {  // an interval of the call's record, unlabelled (no pass kind of its own)
+    if (fp.stage) {  // an interval of the call's record, unlabelled (no pass kind of its own)
       if constexpr (HasLde<E>::value) {
-        if (launch_lde_scale<E>(in, lde->stage, lde->n_in, batch, lde->scale_lo, lde->scale_hi, lo_bits, Ff, st) !=
-            hipSuccess)
+        if (launch_lde_scale<E>(in, fp.stage, fp.n_in, batch, fp.scale_lo, fp.scale_hi, lo_bits, Ff, st) != hipSuccess)
           return NTT_ERR_HIP;
       }
       mark(st);
-      in = lde->stage;
+      in = fp.stage;
     }
     if (npass == 0) {
       PassArgs<E> A = base_args(inverse);
-      A.tw_int = d_tab.get() + off_int[0];
+      A.tw_int = d_tab.get() + off_int[dir][0];
       A.flags = inverse ? 1u : 0u;
       e = launch_naive<E>(in, out, A, batch, st);
       mark(st, "n");
     } else if (npass == 1) {
       PassArgs<E> A = base_args(inverse);
-      A.tw_int = d_tab.get() + off_int[0];
+      A.tw_int = d_tab.get() + off_int[dir][0];
       A.flags = (inverse && !(io && io->no_scale)) ? 1u : 0u;  // no_scale: n^-1 folded in by the caller
       set_fs(A, io, il, FS_MAP_IN | FS_MAP_OUT);
       if (io) A.tw_epi = static_cast<const uint32_t*>(io->tw_epi);
       set_extents(A, io, il);
       if (lde) {  // low-degree extension of at most one tile: one transform per workgroup
-        if constexpr (HasLde<E>::value) {
-          A.src_stride = lde->n_in * MEMW;
-          A.tw_in = lde->lo;
-          A.tw_in_hi = lde->hi;
-          A.dbg_src_n = lde->n_in;
-          e = launch_lde_pass<E>(KIND_SINGLE, (int)r[0], in, out, A, 1, batch, st);
-        } else {
-          e = hipErrorInvalidValue;
-        }
+        apply_first_pass(A, fp);
+        if constexpr (HasLde<E>::value) e = launch_lde_pass<E>(KIND_SINGLE, (int)r[0], in, out, A, 1, batch, st);
+        else e = hipErrorInvalidValue;
         mark(st, "s", r[0]);
-        return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+        return rc_of(e);
       }
       const uint32_t nt = il ? (1u << il) : batch;  // transforms of this launch
       // KIND_ROWS: TILE / n transforms per workgroup (the final pass's block layout: wave-uniform trivial
@@ -1224,10 +826,10 @@ struct PlanImpl final : PlanBase {
       const unsigned rows_log = (unsigned)tile_log_of<E>() - r[0];
       bool rows = false;
       if constexpr (HasRows<E>::value) {
-        bool fast_ok = true;  // the quotient-estimate engines run KIND_ROWS in their FAST form only
-        if constexpr (E::FASTRED) fast_ok = Ff.red_ok != 0;
-        rows = knob::rows() && fast_ok && r[0] >= (unsigned)kRowsMinLog && r[0] <= (unsigned)rows_max_log<E>() &&
-               rows_log >= 1 && nt >= (1u << rows_log) && (nt & ((1u << rows_log) - 1)) == 0;
+        // the quotient-estimate engines run KIND_ROWS in their FAST form only
+        rows = knob::rows() && (!E::FASTRED || fast(Ff)) && r[0] >= (unsigned)kRowsMinLog &&
+               r[0] <= (unsigned)rows_max_log<E>() && rows_log >= 1 && nt >= (1u << rows_log) &&
+               (nt & ((1u << rows_log) - 1)) == 0;
       }
       if (rows) {
         if (!il) {  // the transform index is part of every position: extents over the whole batch
@@ -1249,13 +851,13 @@ struct PlanImpl final : PlanBase {
       uint32_t* work = inplace ? out : d_scratch.get();
       const uint32_t grid = (uint32_t)((n << il) >> tile_log_of<E>());
       if (use_full)
-        if (int rc = ensure_full(inverse ? 1 : 0, st)) return rc;
+        if (int rc = ensure_full(dir, st)) return rc;
       // build the arguments, try the single launch, else launch the passes
       PassArgs<E> PA[8];
-      pass_args(PA, inverse, inplace, il, in2, full0, tw_in, io, lde);
+      pass_args(PA, inverse, inplace, il, fp, io);
       const PassArgs<E>& A = PA[npass - 1];
-      if (!io && !lde && batch == 1 && fused_enabled())
-        if (int rc = NTT_OK; single_launch(PA, in, work, out, inplace, st, rc)) return rc;
+      if (!io && !lde && batch == 1 && single.enabled())
+        if (int rc = NTT_OK; single.launch(PA, in, work, out, inplace, st, rc)) return rc;
       for (unsigned i = 0; i + 1 < npass && e == hipSuccess; ++i) {
         const uint32_t* src = (i == 0) ? in : work;
         if (i == 0 && lde) {
@@ -1266,15 +868,9 @@ struct PlanImpl final : PlanBase {
         }
         mark(st, "c", r[i], PA[i].tw_sh != 0);
       }
-      if (e == hipSuccess && inplace && batch == 1 && ipn_ready(A)) {
+      if (e == hipSuccess && inplace && batch == 1 && single.ipn_ready(A)) {
         // the final pass writes natural positions in place, the digit reversal fused (k_final_ipn)
-        PassArgs<E> B = A;
-        B.flags &= ~2u;
-        B.ipn_sync = d_ipn.get();
-        B.ipn_order = d_ipn.get() + 32 * (2 + ipn_slabs);
-        B.ipn_strips = ipn_strips;
-        B.wd = watchdog(d_ipn.get() + 32 * (1 + ipn_slabs));
-        e = launch_final_ipn<E>((int)r[npass - 1], out, B, grid, st);
+        e = launch_final_ipn<E>((int)r[npass - 1], out, single.ipn_args(A), grid, st);
         mark(st, "i", r[npass - 1]);
       } else if (e == hipSuccess) {
         e = launch_pass<E>(KIND_FINAL, (int)r[npass - 1], work, out, A, grid, batch, st);
@@ -1293,167 +889,9 @@ struct PlanImpl final : PlanBase {
         }
       }
     }
-    return e == hipSuccess ? NTT_OK : NTT_ERR_HIP;
+    return rc_of(e);
   }
 
-  // ---- the single-launch schedules (NTT_PLAN_SINGLE_LAUNCH) and the in-place final pass: state built
-  // on the plan's first use of it (Lazy), each with its own geometry of sync words
-  // knob::single_launch forces the schedule on / off for every plan (A/B); unset: the plan's flag
-  bool fused_enabled() const {
-    const int env = knob::single_launch();
-    return env >= 0 ? env > 0 : (flags & NTT_PLAN_SINGLE_LAUNCH) != 0;
-  }
-  // The sync words of a schedule with inter-workgroup waits (its builder has taken the plan's watchdog
-  // slot, alloc_watch, before its capacity query): `words` zeroed words in `buf`, followed by `tail` when
-  // given (each launch leaves the words zeroed).  Synchronous.
-  bool alloc_sync(DevBuf& buf, size_t words, const std::vector<uint32_t>* tail = nullptr) {
-    const size_t extra = tail ? tail->size() : 0;
-    if (!buf.alloc((words + extra) * 4) || hipMemset(buf.get(), 0, words * 4) != hipSuccess) return false;
-    if (extra && hipMemcpy(buf.get() + words, tail->data(), extra * 4, hipMemcpyHostToDevice) != hipSuccess)
-      return false;
-    return hipDeviceSynchronize() == hipSuccess;
-  }
-  static void fused_verbose(const char* form, uint32_t tiles, uint32_t nwg, uint32_t cap, uint32_t mode = 0) {
-    if (knob::fused_verbose())
-      fprintf(stderr, form, mode), fprintf(stderr, ", %u tiles per pass, %u workgroups (capacity %u)\n", tiles, nwg, cap);
-  }
-  // what both 3-pass single launches need of the passes: full tables for passes 1 and 2 (pass 2: Shoup
-  // pairs), no fused prologue
-  static bool fused3_passes_ok(const PassArgs<E>* PA) {
-    return PA[0].tw_full && PA[1].tw_full && PA[1].tw_sh && !PA[0].src2 && !PA[0].tw_in;
-  }
-
-  // ---- k_fused3 (ntt_fused_impl.hpp): 3-pass FAST 256-bit plans whose passes 1 and 2 take full tables
-  // and whose radices the fused kernel is instantiated for
-  DevBuf d_sync;  // FusedArgs::sync words
-  FusedArgs fargs{};
-  Lazy fused_state;
-  bool fused_ready(const PassArgs<E>* PA) {
-    return fused_state.ready([&] { return build_fused(); }) && fused3_passes_ok(PA);
-  }
-  bool build_fused() {
-    if constexpr (!fused3_engine<E>()) {
-      return false;
-    } else {
-      if (npass != 3 || !use_full || !d_full_sh || !full_sh_ok[1] || !Ff.red_ok || !alloc_watch()) return false;
-      const uint32_t mode = knob::fused_mode();  // 0: the dataflow form (per-tile hand-offs), 1: grid barriers
-      uint32_t cap = 0;
-      if (fused3_capacity<E>((int)r[0], (int)r[1], (int)r[2], device, &cap, mode) != hipSuccess || cap == 0) return false;
-      const FusedGeom g = fused_geometry(tile_log_of<E>(), n, r[0], r[1], r[2], cap, mode);
-      if (!g.ok) return false;  // schedule_ok guarantees it; kept as the kernel's contract
-      fused_verbose("libntt: fused schedule mode %u", g.tiles, g.nwg, cap, mode);
-      if (!alloc_sync(d_sync, g.sync().total())) return false;
-      FusedArgs F{};
-      F.sync = d_sync.get();
-      F.tiles = g.tiles, F.nwg = g.nwg;
-      F.k1_mask = g.k1_mask, F.k1_shift = g.k1_shift;
-      F.cg_log = g.cg_log, F.k2_shift = g.k2_shift, F.t3_log = g.t3_log, F.r2 = g.r2;
-      F.n12 = g.n12, F.n23 = g.n23, F.need12 = g.need12, F.need23 = g.need23;
-      F.rbase = g.rbase;
-      F.dbg = knob::fused_dbg();
-      F.mode = g.mode;
-      F.wd.abort = F.sync + g.sync().abort_word();
-      F.shards = F.sync + g.sync().shards();
-      fargs = F;
-      return true;
-    }
-  }
-
-  // ---- the two-pass single launch on 4096-element tiles (2^20 4-limb plans: k_fused2b, and k_fused2bi
-  // in place; ntt_fused_impl.hpp).  Plain launches of at most the occupancy query's workgroups; the
-  // in-place form needs every one of the 256 final tiles resident.
-  // Sync words: both forms share the in-place form's (FUSED2BI_BARRIERS go words: residency, pass barrier,
-  // final barrier; k_fused2b uses the first), FusedSync in plan_fused.hpp.
-  DevBuf d_sync2;
-  FusedArgs fargs2{}, fargs2_ip{};
-  Lazy fused2_state[2];  // [in place]
-  bool fused2_built(bool inplace) {
-    return fused2_state[inplace ? 1 : 0].ready([&] { return build_fused2(inplace); });
-  }
-  bool fused2_ready(const PassArgs<E>* PA, bool inplace) {
-    return fused2_built(inplace) && PA[0].tw_full && !PA[0].tw_sh && !PA[0].src2 && !PA[0].tw_in;
-  }
-  bool build_fused2(bool inplace) {
-    if constexpr (!fused2_engine<E>()) {
-      return false;
-    } else {
-      if (npass != 2 || r[0] != 10 || r[1] != 10 || !use_full || !Ff.red_ok || !alloc_watch()) return false;
-      const uint32_t tiles = (uint32_t)(n >> tile_log_of<E>()), mode = inplace ? 4u : 3u;
-      uint32_t cap = 0;
-      if (fused2_capacity<E>((int)r[0], (int)r[1], device, &cap, mode) != hipSuccess || cap == 0) return false;
-      if (inplace && cap < tiles) return false;
-      constexpr FusedSync S = fused_sync_barriers(FUSED2BI_BARRIERS);
-      if (!d_sync2 && !alloc_sync(d_sync2, S.total())) return false;
-      FusedArgs F{};
-      F.tiles = tiles;
-      F.nwg = inplace ? tiles : (tiles < cap ? tiles : cap);
-      F.mode = mode;
-      F.rbase = S.rbase;
-      F.sync = d_sync2.get();
-      F.wd.abort = F.sync + S.abort_word();
-      F.shards = F.sync + S.shards();
-      fused_verbose("libntt: two-pass single launch (mode %u)", tiles, F.nwg, cap, mode);
-      (inplace ? fargs2_ip : fargs2) = F;
-      return true;
-    }
-  }
-  // knob::fused_trace_path (diagnostics): the stamps buffer, and its dump after the call
-  DevBuf d_trace;
-  unsigned long long* fused_trace_buffer(uint32_t nwg) {
-    if (!knob::fused_trace_path()) return nullptr;
-    if (!d_trace) (void)d_trace.alloc((size_t)4 * 8 * 1024);
-    return (d_trace && nwg <= 1024) ? d_trace.get<unsigned long long>() : nullptr;
-  }
-  void dump_fused_trace(const FusedArgs& F, bool inplace, hipStream_t st) {
-    std::vector<unsigned long long> h((size_t)4 * F.nwg);
-    if (hipStreamSynchronize(st) != hipSuccess ||
-        hipMemcpy(h.data(), F.trace, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
-      return;
-    if (FILE* f = fopen(knob::fused_trace_path(), "a")) {
-      fprintf(f, "{\"kernel\": \"%s\", \"log_n\": %u, \"nwg\": %u, \"stamps\": [", inplace ? "k_fused2bi" : "k_fused2b",
-              log_n, F.nwg);
-      for (size_t i = 0; i < h.size(); ++i) fprintf(f, "%s%llu", i ? ", " : "", h[i]);
-      fprintf(f, "]}\n");
-      fclose(f);
-    }
-  }
-  bool single_launch_ready() override {
-    if constexpr (fused2_engine<E>())
-      return ensure_full(0, nullptr) == NTT_OK && d_fulls[0] && fused2_built((flags & NTT_PLAN_IN_PLACE) != 0);
-    return false;
-  }
-
-  // ---- the in-place single launch (NTT_PLAN_SINGLE_LAUNCH on an NTT_PLAN_IN_PLACE plan, k_fused3bi):
-  // 3-pass palindromic FAST 256-bit schedules whose tiles all fit the device at once (2^18 .. 2^20)
-  DevBuf d_sync_ip;  // FusedSync of FUSED3BI_BARRIERS barriers: go words for residency and the three grid barriers
-  FusedArgs fargs_ip{};
-  Lazy fused_ip_state;
-  bool fused_ip_ready(const PassArgs<E>* PA) {
-    return fused_ip_state.ready([&] { return build_fused_ip(); }) && fused3_passes_ok(PA);
-  }
-  bool build_fused_ip() {
-    if constexpr (!fused3_engine<E>()) {
-      return false;
-    } else {
-      if (npass != 3 || r[0] != r[2] || !use_full || !d_full_sh || !full_sh_ok[1] || !Ff.red_ok) return false;
-      if (!alloc_watch()) return false;
-      const uint32_t tiles = (uint32_t)(n >> tile_log_of<E>());
-      uint32_t cap = 0;
-      if (fused3_capacity<E>((int)r[0], (int)r[1], (int)r[2], device, &cap, 2) != hipSuccess || cap < tiles) return false;
-      FusedArgs F{};
-      F.tiles = F.nwg = tiles;
-      F.mode = 2;
-      constexpr FusedSync S = fused_sync_barriers(FUSED3BI_BARRIERS);
-      F.rbase = S.rbase;
-      fused_verbose("libntt: in-place single launch", tiles, tiles, cap);
-      if (!alloc_sync(d_sync_ip, S.total())) return false;
-      F.sync = d_sync_ip.get();
-      F.wd.abort = F.sync + S.abort_word();
-      F.shards = F.sync + S.shards();
-      fargs_ip = F;
-      return true;
-    }
-  }
   // bit 0: a bounded wait gave up (the watchdog report, PlanBase::h_watch); then cleared.  Blocking:
   // the device is synchronised first, so the report covers every call enqueued before.
   int device_status(unsigned* bad) override {
@@ -1471,75 +909,33 @@ struct PlanImpl final : PlanBase {
   }
   DevBuf d_dbg;  // debug builds (NTT_DEBUG_CHECKS): the kernels' check-failure bits
 
-  // ---- in-place final pass with the fused digit reversal (NTT_PLAN_IN_PLACE, k_final_ipn)
-  DevBuf d_ipn;  // 32 (2 + slabs) sync words (line 0, one line per slab, the abort line), then the slab order table
-  uint32_t ipn_slabs = 0, ipn_strips = 0;
-  Lazy ipn_state;
-  // knob::ipn off keeps the separate tile-swap pass (A/B)
-  bool ipn_ready(const PassArgs<E>& A) {
-    return ipn_state.ready([&] { return knob::ipn() && build_ipn(A); });
-  }
-  bool build_ipn(const PassArgs<E>& A) {
-    const unsigned tl = tile_log_of<E>(), rp = r[npass - 1];
-    if (npass < 2 || r[0] != rp || rp > 9 || tl < rp || !alloc_watch()) return false;
-    const unsigned mid_log = log_n - r[0] - rp;
-    ipn_slabs = 1u << mid_log;
-    ipn_strips = 1u << (r[0] - (tl - rp));  // R_1 / T, T = TILE / R_p
-    // the deadlock-freedom argument of k_final_ipn needs a slab pair's tiles resident together: at
-    // most 128 per pair, and no more than the device keeps resident
-    if (r[0] < tl - rp || 2 * ipn_strips > 128) return false;
-    if (launch_final_ipn_capacity<E>((int)rp, device) < 2 * ipn_strips) return false;
-    // slab order: m, then its mirror (the final pass's middle-digit reversal, as k_pass computes it)
-    std::vector<uint32_t> order, seen(ipn_slabs, 0);
-    auto rev = [&](uint32_t m) {
-      uint32_t out = 0;
-      for (unsigned i = 0; i < A.nmid; ++i) {
-        out |= (m & ((1u << A.mid_bits[i]) - 1)) << A.mid_off[i];
-        m >>= A.mid_bits[i];
-      }
-      return out;
-    };
-    for (uint32_t m = 0; m < ipn_slabs; ++m) {
-      if (seen[m]) continue;
-      const uint32_t q = rev(m);
-      if (q >= ipn_slabs || rev(q) != m) return false;  // the schedule is not palindromic
-      order.push_back(m);
-      seen[m] = 1;
-      if (q != m) {
-        order.push_back(q);
-        seen[q] = 1;
-      }
-    }
-    return alloc_sync(d_ipn, 32 * (2 + (size_t)ipn_slabs), &order);
-  }
-
   // ---- distributed four-step pieces (ntt_rplan, ntt_amd/csrc/ntt_rplan.cpp)
   int run_fs(const void* in, const void* in2, void* out, unsigned batch, bool inverse, const FsIO& io,
              hipStream_t st) override {
     if (!in || !out || batch == 0 || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
-    auto pin = static_cast<const uint32_t*>(in);
+    auto pin = static_cast<const uint32_t*>(in), pin2 = static_cast<const uint32_t*>(in2);
     auto pout = static_cast<uint32_t*>(out);
-    if (!in2) return run_io(pin, nullptr, pout, batch, inverse, st, nullptr, nullptr, &io);
+    if (!in2) return run_io(pin, pout, batch, inverse, st, FirstPass::plain(), &io);
     if (!inverse) return NTT_ERR_ARG;  // the product is taken at the inverse's load
     const size_t count = (size_t)n * ((io.fs & FS_IL) ? (1ull << io.il) : batch);
     if (polymul_fusable() && npass >= 2) {  // in2 read through the input map like in
       if (int rc = ensure_polymul_table(st)) return rc;
-      return run_io(pin, static_cast<const uint32_t*>(in2), pout, batch, true, st, nullptr, nullptr, &io);
+      return run_io(pin, pout, batch, true, st, FirstPass::product(pin2, d_full_pm.get()), &io);
     }
     if (!(io.fs & (FS_MAP_IN | FS_MAP_OUT))) {  // same layout in and out: the product in place in out
-      if (int rc = pointwise_n(pin, static_cast<const uint32_t*>(in2), pout, count, st)) return rc;
-      return run_io(pout, nullptr, pout, batch, true, st, nullptr, nullptr, &io);
+      if (int rc = pointwise_n(pin, pin2, pout, count, st)) return rc;
+      return run_io(pout, pout, batch, true, st, FirstPass::plain(), &io);
     }
     // a mapped piece (the column pieces of ntt_rplan_inverse_cols_piece): the product gathered into a
     // plan-owned buffer first (out's other pieces may still be in flight)
     if (!d_pw.grow(count * MEMW * 4)) return NTT_ERR_HIP;
     const size_t off = (flags & NTT_PLAN_MONTGOMERY_IO) ? off_rm : off_r2;
-    if (launch_pointwise<E>(pin, static_cast<const uint32_t*>(in2), d_pw.get(), count, Ff, d_tab.get() + off, st,
+    if (launch_pointwise<E>(pin, pin2, d_pw.get(), count, Ff, d_tab.get() + off, st,
                             (io.fs & FS_MAP_IN) ? &io.min : nullptr) != hipSuccess)
       return NTT_ERR_HIP;
     FsIO io2 = io;
     io2.fs &= ~FS_MAP_IN;
-    return run_io(d_pw.get(), nullptr, pout, batch, true, st, nullptr, nullptr, &io2);
+    return run_io(d_pw.get(), pout, batch, true, st, FirstPass::plain(), &io2);
   }
   DevBuf d_pw;  // gathered pointwise products of mapped pieces (run_fs), on first use
 
@@ -1578,9 +974,9 @@ struct PlanImpl final : PlanBase {
   int polymul(void* a, void* b, void* c, hipStream_t st) override {
     if (!a || !b || !c || (flags & NTT_PLAN_TWIDDLE_ONLY)) return NTT_ERR_ARG;
     uint32_t *pa = static_cast<uint32_t*>(a), *pb = static_cast<uint32_t*>(b);
-    if (int rc = run_io(pa, nullptr, pa, 1, false, st)) return rc;
+    if (int rc = run_io(pa, pa, 1, false, st, FirstPass::plain())) return rc;
     if (pb != pa)  // squaring (a == b): one forward transform, then the product of it with itself
-      if (int rc = run_io(pb, nullptr, pb, 1, false, st)) return rc;
+      if (int rc = run_io(pb, pb, 1, false, st, FirstPass::plain())) return rc;
     return inverse_pointwise(pa, pb, c, 1, st);
   }
 
@@ -1593,10 +989,10 @@ struct PlanImpl final : PlanBase {
     auto pc = static_cast<uint32_t*>(c);
     if (polymul_fusable()) {
       if (int rc = ensure_polymul_table(st)) return rc;
-      return run_io(pa, pb, pc, batch, true, st);
+      return run_io(pa, pc, batch, true, st, FirstPass::product(pb, d_full_pm.get()));
     }
     if (int rc = pointwise_n(pa, pb, pc, (size_t)n * batch, st)) return rc;
-    return run_io(pc, nullptr, pc, batch, true, st);
+    return run_io(pc, pc, batch, true, st, FirstPass::plain());
   }
 
   int pointwise_n(const uint32_t* a, const uint32_t* b, uint32_t* c, size_t count, hipStream_t st) {

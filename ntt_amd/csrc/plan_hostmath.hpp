@@ -48,6 +48,22 @@ struct HostField {
   Vec<N> pow_u64(const Vec<N>& base, uint64_t e) const {
     return pow(base, std::vector<uint32_t>{(uint32_t)e, (uint32_t)(e >> 32)});
   }
+  bool below_p(const Vec<N>& a) const {
+    for (int i = N - 1; i >= 0; --i)
+      if (a[i] != M.p[i]) return a[i] < M.p[i];
+    return false;
+  }
+  // limbs64 host words (64-bit, little-endian) -> the element they spell, as N 32-bit words (which may
+  // reach past the caller's limbs: Goldilocks, N = 3 over one 64-bit limb).  False: a bit above the N
+  // words is set, or the value is not below p.  Zero passes: the callers that refuse it check for it.
+  bool canonical(const uint64_t* w, unsigned limbs64, Vec<N>& out) const {
+    out = Vec<N>{};
+    for (int i = 0; i < N && (unsigned)(i / 2) < limbs64; ++i) out[i] = (uint32_t)(w[i / 2] >> (32 * (i % 2)));
+    for (unsigned i = (N + 1) / 2; i < limbs64; ++i)
+      if (w[i]) return false;
+    if ((N & 1) && (unsigned)(N / 2) < limbs64 && (w[N / 2] >> 32)) return false;
+    return below_p(out);
+  }
 };
 
 template <int N>

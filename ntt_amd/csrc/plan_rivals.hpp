@@ -116,7 +116,7 @@ struct Rivals {
     for (unsigned i = 0; i < P.npass && e == hipSuccess; ++i) {
       const unsigned ri = P.r[stk_ord[i]];
       PassArgs<E> A = P.base_args(false);
-      A.tw_int = P.d_tab.get() + P.off_int_f[stk_ord[i]];  // w_R^e for this pass's radix
+      A.tw_int = P.d_tab.get() + P.off_int[0][stk_ord[i]];  // w_R^e for this pass's radix
       A.tw_full = i ? d_stk_tab.get() + stk_off[i] * TABW : nullptr;
       A.log_blk = P.log_n;
       A.lgp = lgp;
@@ -147,7 +147,7 @@ struct Rivals {
     for (unsigned i = 0; i < npass && e == hipSuccess; ++i) {
       const unsigned ri = P.r[stk_ord[i]];
       PassArgs<E> A = P.base_args(false);
-      A.tw_int = P.d_tab.get() + P.off_int_f[stk_ord[i]];  // w_R^e for this pass's radix
+      A.tw_int = P.d_tab.get() + P.off_int[0][stk_ord[i]];  // w_R^e for this pass's radix
       uint32_t* dst = i + 1 == npass ? out : buf;
       if (i == 0) {  // s = 1: contiguous 2^r_0-point DFTs, batched (grid.y chunks of <= 2^15 blocks)
         A.batch_stride = ((size_t)1 << ri) * MEMW;

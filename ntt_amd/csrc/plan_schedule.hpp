@@ -3,6 +3,8 @@
 // C++ only, so that the host checker tests/c/schedule_check.cpp pins every schedule without a GPU.
 #pragma once
 #include <algorithm>
+#include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 
 #include "plan_knobs.hpp"
@@ -185,6 +187,27 @@ static bool schedule_palindrome(unsigned log_n, unsigned tile_log, unsigned rmax
     }
   }
   return false;
+}
+
+// The final pass's middle digits k_2 .. k_{p-1} of a schedule r[0..p), least significant (k_{p-1})
+// first: bits[m] is the digit's width, off[m] its bit offset (relative to R_1) in the output position
+// (PassArgs::mid_bits / mid_off).  Writes p - 2 entries; nothing for p <= 2.
+template <class T>
+static void mid_digits(const unsigned* r, unsigned p, T* bits, T* off) {
+  for (unsigned m = 0; m + 2 < p; ++m) {
+    const unsigned idx = p - 2 - m;  // pass index (0-based) of digit k_{idx+1}
+    bits[m] = r[idx];
+    unsigned o = 0;
+    for (unsigned j = 1; j < idx; ++j) o += r[j];
+    off[m] = o;
+  }
+}
+
+// Two byte ranges share an address (ranges that touch do not).  The calls that read one buffer while
+// other workgroups already write another refuse such arguments.
+static bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
+  return a0 < b1 && b0 < a1;
 }
 
 }  // namespace

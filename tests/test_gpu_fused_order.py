@@ -1,8 +1,9 @@
 """The single launches wait across workgroups, so they need their workgroups resident together
 (ADVICE r05 medium).  Two guarantees, tested deterministically:
 
-* ordering (ntt_plan.cpp FusedSerial): single launches on one device run one after another, whatever
-  streams and plans they come from.  Stream 1 gets a ~1 s sleep kernel, then plan A's single launch;
+* ordering (plan_devmem.hpp FusedSerial, held by plan_single.hpp's launch): single launches on one device
+  run one after another, whatever streams and plans they come from.  Stream 1 gets a ~1 s sleep
+  kernel, then plan A's single launch;
   stream 2 gets plan B's.  B must not have run while stream 1 still sleeps (B waits for A, A for the
   sleep), and both results must equal the default schedule's with no watchdog report.  B is 2^18 (its
   256 workgroups fit beside the sleep kernel), so without the ordering it would finish at once.
