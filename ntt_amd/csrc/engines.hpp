@@ -139,7 +139,6 @@ struct Eng29 {
   // LDS, per CU), which run 2^20 in two passes (10 + 10) instead of three (7 + 7 + 6)
   static constexpr int TILE_LOG = TL_ ? TL_ : ((L <= 9) ? (EPT == 8 ? 11 : NTT_TILE_LOG_256) : 10);
   static constexpr int WAVES_PER_EU = (L <= 9) ? (EPT == 4 ? NTT_WAVES_256 : 2) : 2;
-  static constexpr bool LDS_SPLIT = false;
   // column passes own >= 4 adjacent columns: >= 128-B runs.  The 4096-element tiles also take one
   // column per tile (radix 4096: 2^24 in two passes, 12 + 12, whose 32-B runs meet their three
   // neighbours on one XCD through the XCD-grouped tile order; ntt_plan.cpp make_wide_plan)
@@ -437,7 +436,6 @@ struct Eng32 {
   // twiddles from LDS instead of issuing L1/L2 loads beside the data stream
   static constexpr bool LDS_TW = NTT_P_LDS_TW;
   static constexpr int WAVES_PER_EU = 4;
-  static constexpr bool LDS_SPLIT = false;
   static constexpr bool FASTRED = false;
   struct Tw {
     uint32_t w[1];  // canonical w
@@ -562,7 +560,6 @@ struct Eng64G {
   static constexpr bool SHOUP_OUTER = false;
   static constexpr bool LDS_TW = false;
   static constexpr int WAVES_PER_EU = 4;
-  static constexpr bool LDS_SPLIT = false;
   static constexpr bool FASTRED = false;
   struct Tw {
     uint32_t w[2];  // canonical w (low, high)
@@ -680,7 +677,6 @@ struct Eng31 {
   static constexpr bool SHOUP_OUTER = false;
   static constexpr bool LDS_TW = true;
   static constexpr int WAVES_PER_EU = 4;
-  static constexpr bool LDS_SPLIT = false;
   static constexpr bool FASTRED = false;
   struct Tw {
     uint32_t w[1];  // canonical w
@@ -757,50 +753,29 @@ struct Eng31 {
 
 // ------------------------------------------------------------------------------ LDS (any engine)
 // An element of LDSW words is split into 16-byte planes ([plane][idx]) plus a 4-byte plane per
-// leftover word, so lanes reading consecutive indices hit consecutive slots.
-//
-// With SPLIT (engines that target 3 waves/SIMD) exchanges run in two rounds over the same buffer:
-// part 0 moves planes [0, Q/2) and the leftover words, part 1 planes [Q/2, Q).  Halving the words
-// resident at once halves the tile's LDS (40 KiB instead of 72 KiB for a 2048-element 256-bit
-// tile), which lets 3 workgroups (3 waves per SIMD) share a CU instead of 2.
-template <int LDSW, bool SPLIT>
-struct LdsParts {
-  static constexpr int Q = LDSW / 4, REM = LDSW - 4 * Q;
-  static constexpr int PARTS = (SPLIT && Q >= 2) ? 2 : 1;
-  static constexpr int q_lo(int part) { return PARTS == 1 ? 0 : (part == 0 ? 0 : Q / 2); }
-  static constexpr int q_hi(int part) { return PARTS == 1 ? Q : (part == 0 ? Q / 2 : Q); }
-  static constexpr bool has_rem(int part) { return part == 0; }
-  static constexpr int words(int part) { return 4 * (q_hi(part) - q_lo(part)) + (has_rem(part) ? REM : 0); }
-  static constexpr int max_words() { return words(0) > words(PARTS - 1) ? words(0) : words(PARTS - 1); }
-};
-
-template <int LDSW, bool SPLIT, int E, int PART>
-__device__ __forceinline__ void lds_put_part(uint32_t* lds, uint32_t idx, const uint32_t (&x)[LDSW]) {
-  using P = LdsParts<LDSW, SPLIT>;
+// leftover word, so lanes reading consecutive indices hit consecutive slots.  E: elements per plane.
+template <int LDSW, int E>
+__device__ __forceinline__ void lds_put(uint32_t* lds, uint32_t idx, const uint32_t (&x)[LDSW]) {
+  constexpr int Q = LDSW / 4;
   uint4* l4 = reinterpret_cast<uint4*>(lds);
 #pragma unroll
-  for (int q = P::q_lo(PART); q < P::q_hi(PART); ++q)
-    l4[(q - P::q_lo(PART)) * E + idx] = make_uint4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
-  if constexpr (P::has_rem(PART)) {
-    uint32_t* l1 = lds + 4 * (P::q_hi(PART) - P::q_lo(PART)) * E;
+  for (int q = 0; q < Q; ++q) l4[q * E + idx] = make_uint4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
+  uint32_t* l1 = lds + 4 * Q * E;
 #pragma unroll
-    for (int r = 4 * P::Q; r < LDSW; ++r) l1[(r - 4 * P::Q) * E + idx] = x[r];
-  }
+  for (int r = 4 * Q; r < LDSW; ++r) l1[(r - 4 * Q) * E + idx] = x[r];
 }
-template <int LDSW, bool SPLIT, int E, int PART>
-__device__ __forceinline__ void lds_get_part(uint32_t (&x)[LDSW], const uint32_t* lds, uint32_t idx) {
-  using P = LdsParts<LDSW, SPLIT>;
+template <int LDSW, int E>
+__device__ __forceinline__ void lds_get(uint32_t (&x)[LDSW], const uint32_t* lds, uint32_t idx) {
+  constexpr int Q = LDSW / 4;
   const uint4* l4 = reinterpret_cast<const uint4*>(lds);
 #pragma unroll
-  for (int q = P::q_lo(PART); q < P::q_hi(PART); ++q) {
-    const uint4 v = l4[(q - P::q_lo(PART)) * E + idx];
+  for (int q = 0; q < Q; ++q) {
+    const uint4 v = l4[q * E + idx];
     x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
   }
-  if constexpr (P::has_rem(PART)) {
-    const uint32_t* l1 = lds + 4 * (P::q_hi(PART) - P::q_lo(PART)) * E;
+  const uint32_t* l1 = lds + 4 * Q * E;
 #pragma unroll
-    for (int r = 4 * P::Q; r < LDSW; ++r) x[r] = l1[(r - 4 * P::Q) * E + idx];
-  }
+  for (int r = 4 * Q; r < LDSW; ++r) x[r] = l1[(r - 4 * Q) * E + idx];
 }
 
 }  // namespace ntt

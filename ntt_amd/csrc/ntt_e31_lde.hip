@@ -1,5 +1,5 @@
 // Eng31 (primes below 2^31, 4-B elements): k_pass instantiations of the low-degree-extension first passes (PRO_LDE: KIND_COLUMN, KIND_SINGLE).
-#include "ntt_kernels_impl.hpp"
+#include "ntt_lde_impl.hpp"
 namespace ntt {
 NTT_INSTANTIATE_LDE(Eng31)
 }  // namespace ntt

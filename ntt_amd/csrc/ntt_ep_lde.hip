@@ -1,5 +1,5 @@
 // EngP: k_pass instantiations of the low-degree-extension first passes (PRO_LDE: KIND_COLUMN, KIND_SINGLE).
-#include "ntt_kernels_impl.hpp"
+#include "ntt_lde_impl.hpp"
 namespace ntt {
 NTT_INSTANTIATE_LDE(EngP)
 }  // namespace ntt

@@ -16,10 +16,12 @@
 // LDS exchanges (16-B planes) in between: the wave64 replacement for the reference's shared-memory
 // radix-2 rounds (SSIP_NTT_stage1 GZKP-NTT.cu:1297-1357) and its cub::WarpExchange /
 // parallel-load staging (test-cub-WarpExchange.cu:6-64, parallel-load.cu:114-193).
-// This header: the pass tile, k_pass and k_final_ipn, the table builders, the rival schedules and the
-// utility kernels.  Families with translation units of their own live beside it: the single-launch
-// schedules in ntt_fused_impl.hpp, the row-major matrix passes in ntt_mat_impl.hpp, the FRI fold in
-// ntt_fold_impl.hpp.
+// This header: the pass tile, k_pass and its launchers, nothing else.  Every other kernel family has a
+// header of its own beside it: the single-launch schedules in ntt_fused_impl.hpp, the row-major matrix
+// passes in ntt_mat_impl.hpp, the PRO_LDE launchers in ntt_lde_impl.hpp, the in-place final pass and
+// digit reversal in ntt_inplace_impl.hpp, the table builders in ntt_tables_impl.hpp, the rival
+// schedules in ntt_rivals_impl.hpp, the element-wise kernels in ntt_elementwise_impl.hpp and the FRI
+// fold in ntt_fold_impl.hpp.
 #pragma once
 #include <cstdlib>
 #include <utility>
@@ -234,10 +236,11 @@ __device__ __forceinline__ void substage(uint32_t (&x)[E::EPT][E::W], uint32_t (
   constexpr int EPT = E::EPT;
   constexpr int pqb = S::qb(s - 1), PQ = 1 << pqb, PG = EPT / PQ, psb = S::logsig(s - 1), plN = S::logN(s - 1);
   constexpr int qb = S::qb(s), Q = 1 << qb, G = EPT / Q, sb = S::logsig(s), lN = S::logN(s);
-  using P = LdsParts<E::LDSW, E::LDS_SPLIT>;
-  static_for<P::PARTS>([&](auto PT) {
-    constexpr int part = PT;
-    if constexpr (s > 1 || part > 0) __syncthreads();  // everyone finished reading the previous round
+  // The exchange stays inside one lambda of its own.  Written straight into this function it is the same
+  // program, but the compiler then forms the LDS addresses of the radix-256 tiles of 73 kernels with other
+  // instructions (tools/kernel_manifest.py), and a refactor does not change device code.
+  static_for<1>([&](auto) {
+    if constexpr (s > 1) __syncthreads();  // everyone finished reading the previous round
     static_for<PG>([&](auto J) {
       constexpr int j = J;
       const uint32_t g = pil[j];
@@ -245,7 +248,7 @@ __device__ __forceinline__ void substage(uint32_t (&x)[E::EPT][E::W], uint32_t (
       static_for<PQ>([&](auto K) {
         constexpr int k = K;
         const uint32_t pi = (rho << plN) + cp + (k << psb);
-        lds_put_part<E::LDSW, E::LDS_SPLIT, TE, part>(lds, lds_slot<T>(cl[j], pi), x[j * PQ + brev_bits(k, pqb)]);
+        lds_put<E::LDSW, TE>(lds, lds_slot<T>(cl[j], pi), x[j * PQ + brev_bits(k, pqb)]);
       });
     });
     __syncthreads();
@@ -257,7 +260,7 @@ __device__ __forceinline__ void substage(uint32_t (&x)[E::EPT][E::W], uint32_t (
       static_for<Q>([&](auto D) {
         constexpr int d = D;
         const uint32_t pi = (rho << lN) + cp + (d << sb);
-        lds_get_part<E::LDSW, E::LDS_SPLIT, TE, part>(x[j * Q + d], lds, lds_slot<T>(c, pi));
+        lds_get<E::LDSW, TE>(x[j * Q + d], lds, lds_slot<T>(c, pi));
       });
     });
   });
@@ -322,7 +325,7 @@ enum : int { PRO_NONE = 0, PRO_PW = 1, PRO_COSET = 2, PRO_LDE = 3 };
 #ifndef NTT_COL_R32_BELOW
 #define NTT_COL_R32_BELOW 8
 #endif
-// ---- in-place final pass with the digit reversal fused (NTT_PLAN_IN_PLACE; k_final_ipn below).
+// ---- in-place final pass with the digit reversal fused (NTT_PLAN_IN_PLACE; k_final_ipn, ntt_inplace_impl.hpp).
 // The final pass's outputs of slab `mid` belong in slab `midrev` (the palindromic schedule makes the
 // digit reversal an involution), so a tile may store only after every tile of slab midrev has READ
 // its elements (an anti-dependency: nothing handed-off is loaded, so no acquire is needed).  Reads
@@ -479,7 +482,7 @@ __host__ __device__ constexpr int pass_tile_te() {
 }
 template <class E, int LOGR, int KIND>
 __host__ __device__ constexpr int pass_lds_words() {
-  return pass_tile_te<E, LOGR, KIND>() * LdsParts<E::LDSW, E::LDS_SPLIT>::max_words();
+  return pass_tile_te<E, LOGR, KIND>() * E::LDSW;
 }
 template <class E, int KIND, bool FULLTW>
 __host__ __device__ constexpr bool pass_ltw() {
@@ -951,831 +954,6 @@ void k_pass(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const 
   pass_tile<E, LOGR, KIND, FULLTW, FAST, PRO, SRC_USER, FSM, SHTW>(src, dst, A, w, blockIdx.y, lds, lds_tw);
 }
 
-// In-place final pass with the fused digit reversal: one tile per workgroup, tiles taken from a
-// ticket counter in slab-pair order (slab m's tiles, then slab rev(m)'s), so that a tile waits only
-// for tiles of its own pair.  Deadlock-free at any residency: every ticket below the newest pair's
-// was taken by a running workgroup, those pairs complete, and a pair has 2 R_1 / T <= 128 tiles.
-// The last workgroup out re-zeroes the counters for the next launch.
-template <class E, int LOGR>
-__global__ __launch_bounds__((1 << E::TILE_LOG) / E::EPT) __attribute__((amdgpu_waves_per_eu(E::WAVES_PER_EU)))
-void k_final_ipn(uint32_t* data, const PassArgs<E> A) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[pass_lds_words<E, LOGR, KIND_FINAL>()];
-  __shared__ __attribute__((aligned(16))) uint32_t lds_tw[pass_ltw<E, KIND_FINAL, false>() ? (1 << LOGR) * E::TW : 1];
-  __shared__ uint32_t s_w, s_last;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) {
-    const uint32_t tk = __hip_atomic_fetch_add(A.ipn_sync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t slab = A.ipn_order[tk / A.ipn_strips], strip = tk % A.ipn_strips;
-    s_w = (strip << (A.log_n - A.r1 - LOGR)) | slab;  // the final pass's tile index: (k1 group, mid)
-  }
-  __syncthreads();
-  const uint32_t w = s_w;
-  if constexpr (E::FASTRED) {
-    if (A.F.red_ok)
-      pass_tile<E, LOGR, KIND_FINAL, TW_TWO_LEVEL, RED_FAST, PRO_NONE, SRC_CALLER, FSM_NONE, OUTER_MONT, STORE_PLAIN, TILE_ONCE, IPN_SLAB>(
-          data, data, A, w, 0, lds, lds_tw);
-    else
-      pass_tile<E, LOGR, KIND_FINAL, TW_TWO_LEVEL, RED_GENERIC, PRO_NONE, SRC_CALLER, FSM_NONE, OUTER_MONT, STORE_PLAIN, TILE_ONCE, IPN_SLAB>(
-          data, data, A, w, 0, lds, lds_tw);
-  } else {
-    pass_tile<E, LOGR, KIND_FINAL, TW_TWO_LEVEL, RED_GENERIC, PRO_NONE, SRC_CALLER, FSM_NONE, OUTER_MONT, STORE_PLAIN, TILE_ONCE, IPN_SLAB>(
-        data, data, A, w, 0, lds, lds_tw);
-  }
-  if (t == 0)
-    s_last = __hip_atomic_fetch_add(A.ipn_sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  __syncthreads();
-  if (s_last) {  // nobody touches the counters again in this launch
-    const uint32_t slabs = (uint32_t)(gridDim.x / A.ipn_strips);
-    for (uint32_t m = t; m < slabs; m += blockDim.x) {
-      A.ipn_sync[32 * (1 + m)] = 0u;
-      A.ipn_sync[32 * (1 + m) + 1] = 0u;
-    }
-    if (t == 0) {
-      A.ipn_sync[0] = A.ipn_sync[1] = 0u;
-      if (A.wd.abort) *A.wd.abort = 0u;
-    }
-  }
-}
-
-// The host function of k_final_ipn<E, logr>, or null where the radix has no instance: the launcher and
-// the capacity query take their kernel from here
-template <class E>
-auto final_ipn_kernel(int logr) -> void (*)(uint32_t*, const PassArgs<E>) {
-  void (*k)(uint32_t*, const PassArgs<E>) = nullptr;
-  (void)with_radix<3, 9>(logr, [&](auto R) {
-    if constexpr (R <= tile_log_of<E>() - E::MIN_COLS_LOG) k = &k_final_ipn<E, R>;
-    return hipSuccess;
-  });
-  return k;
-}
-
-template <class E>
-hipError_t launch_final_ipn(int logr, uint32_t* data, const PassArgs<E>& A, uint32_t grid, hipStream_t st) {
-  const auto k = final_ipn_kernel<E>(logr);
-  if (!k) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k, dim3(grid), dim3((1 << tile_log_of<E>()) / E::EPT), 0, st, data, A);
-  return hipGetLastError();
-}
-
-// Workgroups of k_final_ipn<E, logr> the device keeps resident at once (occupancy x CUs; 0 if the
-// query fails or the radix has no instance)
-template <class E>
-uint32_t launch_final_ipn_capacity(int logr, int device) {
-  int cus = 0, per = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
-  const auto k = final_ipn_kernel<E>(logr);
-  if (!k || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void*>(k),
-                                                         (1 << tile_log_of<E>()) / E::EPT, 0) != hipSuccess)
-    return 0;
-  return (per > 0 && cus > 0) ? (uint32_t)per * (uint32_t)cus : 0u;
-}
-
-// Element-wise kernels run as grid-stride loops over at most 2^20 workgroups of 256 threads:
-// grid.x * blockDim.x stays far below HIP's 2^32-thread launch limit at every supported size
-// (2^32-element BLS12-381 vectors included).
-__host__ __device__ constexpr uint32_t grid_1d(size_t count) {
-  return (uint32_t)((count + 255) / 256 < (size_t(1) << 20) ? (count + 255) / 256 : (size_t(1) << 20));
-}
-#define NTT_GRID_STRIDE(idx, count) \
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (count); idx += (size_t)gridDim.x * blockDim.x)
-
-// O(n^2) transform for tiny n (n <= 4): X_k = sum_j x_j w^(jk); tw_int holds w^e, e < n.
-template <class E>
-__global__ void k_dft_naive(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, const PassArgs<E> A) {
-  const uint32_t n = 1u << A.log_n;
-  const uint32_t k = threadIdx.x;
-  const size_t boff = (size_t)blockIdx.y * A.batch_stride;
-  uint32_t acc[E::W];
-  if (k < n) {
-    // acc = x_0 * w^0 (Montgomery by w^0 = R brings it to the engine's residue form)
-    uint32_t v[E::W];
-    typename E::Tw w;
-    E::load(acc, src + boff, 0);
-    E::tload(w, A.tw_int, 0);
-    E::mul(acc, w, A.F);
-#pragma unroll 1
-    for (uint32_t j = 1; j < n; ++j) {
-      E::load(v, src + boff, j);
-      E::tload(w, A.tw_int, (j * k) & (n - 1));
-      E::mul(v, w, A.F);
-      E::template bfly_l<E::IN>(acc, v, A.F);  // acc <- acc + v (the difference is discarded)
-      E::template reduce<2 * E::IN, E::IN>(acc, A.F);
-    }
-    if (A.flags & 1u) E::mul(acc, A.F.ninv, A.F);
-  }
-  __syncthreads();  // every thread has read src before anyone writes dst (in-place use)
-  if (k < n) E::template store<E::IN>(dst + boff, k, acc, A.F);
-}
-
-// Per-pass outer-twiddle table of a column pass with radix 2^log_r and T = 2^log_t columns per
-// workgroup: entry (c, k) = w_n^((c*k) << log_m) R_e mod p (R_e the engine's Montgomery radix) at
-// [c >> log_t][k][c mod T], canonical in the HBM element format, built on the device from the
-// two-level tables (lo_s = lo R_e, so lo_s * hi = w R_e).  With clo/chi (two-level tables of a coset
-// shift c in the same format) the entry is also multiplied by c^col.
-template <class E>
-__global__ void k_build_tw(uint32_t* __restrict__ out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,
-                           const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, uint32_t lo_bits,
-                           const typename E::Args F, const uint32_t* __restrict__ clo,
-                           const uint32_t* __restrict__ chi) {
-  NTT_GRID_STRIDE(idx, count) {
-    const size_t k = (idx >> log_t) & ((1ull << log_r) - 1);
-    const size_t c = ((idx >> (log_t + log_r)) << log_t) + (idx & ((1ull << log_t) - 1));
-    const size_t e = (c * k) << log_m;
-    typename E::Tw a, b;
-    E::tload(a, lo, (uint32_t)(e & ((1ull << lo_bits) - 1)));
-    E::tload(b, hi, (uint32_t)(e >> lo_bits));
-    E::mul(a.w, b, F);
-    if (clo) {  // c^col R_e = clo[col & mask] * chi[col >> lo_bits]; mulv removes one R_e
-      typename E::Tw u, v;
-      E::tload(u, clo, (uint32_t)(c & ((1ull << lo_bits) - 1)));
-      E::tload(v, chi, (uint32_t)(c >> lo_bits));
-      E::mul(u.w, v, F);
-      E::mulv(a.w, u.w, F);
-    }
-    E::template store<E::MUL_OUT, false, E::TABW>(out, idx, a.w, F);  // outer-twiddle tables: E::TABW words
-  }
-}
-
-template <class E>
-hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,
-                           const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F,
-                           hipStream_t st, const uint32_t* clo, const uint32_t* chi) {
-  hipLaunchKernelGGL((k_build_tw<E>), dim3(grid_1d(count)), dim3(256), 0, st, out, count, log_r,
-                     log_t, log_m, lo, hi, lo_bits, F, clo, chi);
-  return hipGetLastError();
-}
-
-// NTT_PLAN_NAIVE (the reference's `naive` rival, GZKP-NTT.cu:59-71 / big-num.cu:67-104): the power
-// table entry i = w_n^i R_e mod p, i < count, canonical in the element format (E::TABW words) -- the
-// reference's `roots` table (GZKP-NTT.cu:81-83), built on the device from the two-level tables.
-template <class E>
-__global__ void k_build_pow(uint32_t* __restrict__ out, size_t count, const uint32_t* __restrict__ lo,
-                            const uint32_t* __restrict__ hi, uint32_t lo_bits, const typename E::Args F) {
-  NTT_GRID_STRIDE(i, count) {
-    typename E::Tw a, b;
-    E::tload(a, lo, i & ((size_t(1) << lo_bits) - 1));
-    E::tload(b, hi, i >> lo_bits);
-    E::mul(a.w, b, F);
-    E::template store<E::MUL_OUT, false, E::TABW>(out, i, a.w, F);
-  }
-}
-
-template <class E>
-hipError_t launch_build_pow(uint32_t* out, size_t count, const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits,
-                            const typename E::Args& F, hipStream_t st) {
-  hipLaunchKernelGGL((k_build_pow<E>), dim3(grid_1d(count)), dim3(256), 0, st, out, count, lo, hi, lo_bits, F);
-  return hipGetLastError();
-}
-
-// One radix-2 DIT round of the `naive` rival over a bit-reversed vector: butterfly id < n/2 pairs
-// pos = 2 (id - off) + off and pos + s (s = 2^log_s, off = id mod s) as (a + w b, a - w b) with
-// w = w_n^(off n / 2s) -- the reference kernel's indexing (GZKP-NTT.cu:59-71), one thread per
-// butterfly, canonical in and out (the product through the element-format power table: mulv).
-// HBM-bound by construction: every round reads and writes the whole vector.  src and dst alias (every
-// round but the last runs in place), so neither is __restrict__: each thread reads its two
-// elements before it writes them, and no other thread touches them in the round.
-template <class E>
-__global__ void k_naive_round(const uint32_t* src, uint32_t* dst, uint32_t log_n,
-                              uint32_t log_s, const uint32_t* __restrict__ pw, const typename E::Args F) {
-  const size_t half = size_t(1) << (log_n - 1), s = size_t(1) << log_s;
-  NTT_GRID_STRIDE(id, half) {
-    const size_t off = id & (s - 1), pos = ((id - off) << 1) + off;
-    uint32_t a[E::W], b[E::W], w[E::W];
-    E::load(a, src, pos);
-    E::load(b, src, pos + s);
-    E::template load<E::TABW>(w, pw, off << (log_n - 1 - log_s));
-    E::mulv(b, w, F);  // w R_e: the Montgomery product leaves w b, < 3p (Eng29) / < 2p (Eng32)
-    E::template bfly_l<E::IN>(a, b, F);
-    E::template store<2 * E::IN>(dst, pos, a, F);
-    E::template store<2 * E::IN>(dst, pos + s, b, F);
-  }
-}
-
-// One radix-2 round of the `naive_no_swap` rival (GZKP-NTT.cu:237-258): butterfly i < n/2 reads
-// x[i] and x[i + n/2], multiplies the second by w = w_n^(k n / 2s) (k = i mod s, s = 2^log_s: the
-// reference's roots[k * (len / (stride << 1))]) and writes a + w b to y[2i - k], a - w b to
-// y[2i - k + s] -- a radix-2 Stockham autosort: natural order in and out after log2 n rounds.
-// src != dst (ping-pong).  HBM-bound by construction, like k_naive_round.
-template <class E>
-__global__ void k_noswap_round(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t log_n,
-                               uint32_t log_s, const uint32_t* __restrict__ pw, const typename E::Args F) {
-  const size_t half = size_t(1) << (log_n - 1), s = size_t(1) << log_s;
-  NTT_GRID_STRIDE(i, half) {
-    const size_t k = i & (s - 1), j = (i << 1) - k;
-    uint32_t a[E::W], b[E::W], w[E::W];
-    E::load(a, src, i);
-    E::load(b, src, i + half);
-    E::template load<E::TABW>(w, pw, k << (log_n - 1 - log_s));
-    E::mulv(b, w, F);  // w R_e: the Montgomery product leaves w b
-    E::template bfly_l<E::IN>(a, b, F);
-    E::template store<2 * E::IN>(dst, j, a, F);
-    E::template store<2 * E::IN>(dst, j + s, b, F);
-  }
-}
-
-template <class E>
-hipError_t launch_noswap_round(const uint32_t* src, uint32_t* dst, uint32_t log_n, uint32_t log_s, const uint32_t* pw,
-                               const typename E::Args& F, hipStream_t st) {
-  if (log_n == 0 || log_s >= log_n || src == dst) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_noswap_round<E>), dim3(grid_1d(size_t(1) << (log_n - 1))), dim3(256), 0, st, src, dst, log_n,
-                     log_s, pw, F);
-  return hipGetLastError();
-}
-
-template <class E>
-hipError_t launch_naive_round(const uint32_t* src, uint32_t* dst, uint32_t log_n, uint32_t log_s, const uint32_t* pw,
-                              const typename E::Args& F, hipStream_t st) {
-  if (log_n == 0 || log_s >= log_n) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_naive_round<E>), dim3(grid_1d(size_t(1) << (log_n - 1))), dim3(256), 0, st, src, dst, log_n,
-                     log_s, pw, F);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------- bealto / bellperson rivals
-// The reference's radix-2^deg Stockham family (bealto.com's group FFT as bellperson ships it,
-// FIELD_radix_fft_revised, GZKP-NTT.cu:391-464, and the four "improved" kernels, GZKP-NTT.cu:556-630,
-// 632-719, 892-989, 1077-1210; ntt.h NTT_PLAN_BELLPERSON / NTT_PLAN_IMPROVED_V1..V4) as ONE kernel
-// with the variant as a template argument: they compute the same round and differ only in how
-// threads, groups and LDS rows are mapped, which is what they are kept for (comparison).  A round
-// takes groups `index` of 2^deg elements x[index + i t] (t = n >> deg), multiplies element i by
-// w_n^(e i), e = (n >> lgp >> deg) (index mod 2^lgp) (from the two-level tables: the reference raises
-// FIELD_pow_lookup's twiddle per thread), runs deg radix-2 rounds in LDS with the pq table and writes
-// y[((index - k) << deg) + k + i 2^lgp].  lsize = 2^(deg-1) threads per group, two elements each.
-//   bellperson: inputs land bit-reversed in LDS, DIT rounds (twiddle, then butterfly), natural out;
-//   v1:         DIF rounds (butterfly, then twiddle), bit-reversed out; 2^log_g groups per workgroup;
-//   v2:         loads on the transposed map (thread -> group tid mod G: coalesced x[index + i t]);
-//   v3:         and stores on it too when lgp > 0 (consecutive k: coalesced y);
-//   v4:         and LDS rows of 2 lsize + 1 elements (the reference's bank-conflict padding).
-// Lazy bounds (Eng29): loads < p, input products < 3p, every butterfly's outputs brought back < 4p.
-__device__ __forceinline__ uint32_t brev_rt(uint32_t v, uint32_t bits) {
-  return bits ? __builtin_bitreverse32(v) >> (32u - bits) : 0u;
-}
-template <class E>
-__device__ __forceinline__ void lds_put_el(uint32_t* u, uint32_t slot, const uint32_t (&v)[E::W]) {
-#pragma unroll
-  for (int w = 0; w < E::W; ++w) u[(size_t)slot * E::W + w] = v[w];
-}
-template <class E>
-__device__ __forceinline__ void lds_get_el(uint32_t (&v)[E::W], const uint32_t* u, uint32_t slot) {
-#pragma unroll
-  for (int w = 0; w < E::W; ++w) v[w] = u[(size_t)slot * E::W + w];
-}
-template <class E, int V>
-__global__ __launch_bounds__(1024) void k_bealto(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
-                                                 const PassArgs<E> A, const BealtoArgs B) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t u_g[];
-  const uint32_t deg = B.deg, lsz = 1u << (deg - 1), G = 1u << B.log_g, tid = threadIdx.x;
-  const size_t t = (size_t)1 << (B.log_n - deg), p = (size_t)1 << B.lgp;
-  const uint32_t rl = 2 * lsz + (V == BEALTO_V4 ? 1u : 0u);  // one group's LDS row, elements
-  // compute map: group gid, lane lid; load map: transposed from v2 on
-  const uint32_t lid = tid & (lsz - 1), gid = tid >> (deg - 1);
-  const uint32_t gid_r = V >= BEALTO_V2 ? (tid & (G - 1)) : gid, lid_r = V >= BEALTO_V2 ? (tid >> B.log_g) : lid;
-  const size_t index = (size_t)blockIdx.x * G + gid, index_r = (size_t)blockIdx.x * G + gid_r;
-  const size_t k = index & (p - 1), k_r = index_r & (p - 1);
-  {
-    const size_t e = (t >> B.lgp) * k_r;  // w_n^(e i): < n for i < 2^deg
-    uint32_t* u = u_g + (size_t)gid_r * rl * E::W;
-#pragma unroll
-    for (uint32_t j = 0; j < 2; ++j) {
-      const uint32_t i = 2 * lid_r + j;
-      uint32_t v[E::W];
-      E::load(v, src, index_r + i * t);
-      const size_t ei = e * i;
-      typename E::Tw tl, th;
-      E::tload(tl, A.tw_lo, (uint32_t)(ei & ((1u << A.lo_bits) - 1)));
-      E::tload(th, A.tw_hi, (uint32_t)(ei >> A.lo_bits));
-      E::mul(tl.w, th, A.F);  // (lo R_e) hi
-      E::mulv(v, tl.w, A.F);  // v w_n^(e i), < 3p
-      lds_put_el<E>(u, V == BEALTO_BELLPERSON ? brev_rt(i, deg) : i, v);
-    }
-  }
-  __syncthreads();
-  {
-    uint32_t* u = u_g + (size_t)gid * rl * E::W;
-    const uint32_t pqshift = B.max_deg - deg;
-    for (uint32_t s = 0; s < deg; ++s) {
-      const uint32_t rnd = V == BEALTO_BELLPERSON ? deg - 1 - s : s;
-      const uint32_t bit = lsz >> rnd, di = lid & (bit - 1), i0 = (lid << 1) - di, i1 = i0 + bit;
-      uint32_t a[E::W], b[E::W];
-      lds_get_el<E>(a, u, i0);
-      lds_get_el<E>(b, u, i1);
-      typename E::Tw w;
-      if (di) E::tload(w, A.tw_int, di << rnd << pqshift);  // w_{2^(deg - rnd)}^di
-      if constexpr (V == BEALTO_BELLPERSON) {  // DIT: twiddle, then butterfly
-        if (di) E::mul(b, w, A.F);
-        E::template bfly_l<E::IN>(a, b, A.F);
-        E::template reduce<2 * E::IN, E::IN>(b, A.F);
-      } else {  // DIF: butterfly, then twiddle
-        E::template bfly_l<E::IN>(a, b, A.F);
-        if (di) E::mul(b, w, A.F);
-        else E::template reduce<2 * E::IN, E::IN>(b, A.F);
-      }
-      E::template reduce<2 * E::IN, E::IN>(a, A.F);
-      lds_put_el<E>(u, i0, a);
-      lds_put_el<E>(u, i1, b);
-      __syncthreads();
-    }
-  }
-  // stores: the load map for v3 / v4 after the first round (consecutive k: coalesced), else the compute map
-  const bool rmap = V >= BEALTO_V3 && B.lgp != 0;
-  const size_t gi = rmap ? index_r : index, kk = rmap ? k_r : k;
-  const uint32_t li = rmap ? lid_r : lid;
-  const uint32_t* u = u_g + (size_t)(rmap ? gid_r : gid) * rl * E::W;
-  const size_t base = ((gi - kk) << deg) + kk;
-#pragma unroll
-  for (uint32_t j = 0; j < 2; ++j) {
-    const uint32_t i = li + j * lsz;
-    uint32_t v[E::W];
-    lds_get_el<E>(v, u, V == BEALTO_BELLPERSON ? i : brev_rt(i, deg));
-    E::template store<E::IN>(dst, base + i * p, v, A.F);
-  }
-}
-
-template <class E>
-hipError_t launch_bealto(int variant, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, const BealtoArgs& B,
-                         hipStream_t st) {
-  if constexpr (!HasStockham<E>::value) {
-    return hipErrorInvalidValue;
-  } else {
-    if (B.deg < 1 || B.deg > B.max_deg || B.deg > B.log_n || B.log_n - B.deg < B.log_g || src == dst)
-      return hipErrorInvalidValue;
-    const uint32_t threads = (1u << (B.deg - 1)) << B.log_g;
-    const size_t grid = ((size_t)1 << (B.log_n - B.deg)) >> B.log_g;
-    const size_t lds = ((size_t)((2u << (B.deg - 1)) + (variant == BEALTO_V4 ? 1u : 0u)) << B.log_g) * E::W * 4;
-    if (threads > 1024 || grid > 0x7fffffffull || lds > 64 * 1024) return hipErrorInvalidValue;
-    const dim3 g((uint32_t)grid), b(threads);
-    switch (variant) {
-      case BEALTO_BELLPERSON: hipLaunchKernelGGL((k_bealto<E, BEALTO_BELLPERSON>), g, b, lds, st, src, dst, A, B); break;
-      case BEALTO_V1: hipLaunchKernelGGL((k_bealto<E, BEALTO_V1>), g, b, lds, st, src, dst, A, B); break;
-      case BEALTO_V2: hipLaunchKernelGGL((k_bealto<E, BEALTO_V2>), g, b, lds, st, src, dst, A, B); break;
-      case BEALTO_V3: hipLaunchKernelGGL((k_bealto<E, BEALTO_V3>), g, b, lds, st, src, dst, A, B); break;
-      case BEALTO_V4: hipLaunchKernelGGL((k_bealto<E, BEALTO_V4>), g, b, lds, st, src, dst, A, B); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-}
-
-// k_build_tw's table as Shoup pairs: entry (c, k) = (w, floor(w B / p)) with w = w_n^((c*k) << log_m)
-// canonical, in the engine's twiddle format (E::TW words).  t = lo_s * hi = w B mod p; w = t / B
-// (Montgomery product by 1); floor(w B / p) = (-(w B mod p)) p^-1 mod B (shoup_ws29).
-template <class E>
-__global__ void k_build_tw_sh(uint32_t* __restrict__ out, size_t count, uint32_t log_r, uint32_t log_t,
-                              uint32_t log_m, const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi,
-                              uint32_t lo_bits, const typename E::Args F, const uint32_t* __restrict__ pinvB) {
-  constexpr int L = E::W;
-  NTT_GRID_STRIDE(idx, count) {
-    const size_t k = (idx >> log_t) & ((1ull << log_r) - 1);
-    const size_t c = ((idx >> (log_t + log_r)) << log_t) + (idx & ((1ull << log_t) - 1));
-    const size_t e = (c * k) << log_m;
-    typename E::Tw a, b;
-    E::tload(a, lo, (uint32_t)(e & ((1ull << lo_bits) - 1)));
-    E::tload(b, hi, (uint32_t)(e >> lo_bits));
-    E::mul(a.w, b, F);  // w B mod p, < 3p
-    uint32_t wr[L], w[L], one[L], t[L], ws[L], pib[L];
-#pragma unroll
-    for (int i = 0; i < L; ++i) {
-      wr[i] = a.w[i];
-      one[i] = i == 0 ? 1u : 0u;
-      pib[i] = pinvB[i];
-    }
-    E::template reduce<4, 1, false>(wr, F);  // canonical w B mod p
-#pragma unroll
-    for (int i = 0; i < L; ++i) w[i] = wr[i];
-    E::mulv(w, one, F);  // w, < 3p
-    E::template reduce<4, 1, false>(w, F);
-    neg29<L>(t, wr);
-    mullo29<L>(ws, t, pib);
-    uint32_t o[E::TW];
-#pragma unroll
-    for (int i = 0; i < E::TW; ++i) o[i] = i < L ? w[i] : (i < 2 * L ? ws[i - L] : 0u);
-    uint4* p = reinterpret_cast<uint4*>(out + idx * E::TW);
-#pragma unroll
-    for (int q = 0; q < E::TW / 4; ++q) p[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-  }
-}
-
-template <class E>
-hipError_t launch_build_tw_sh(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,
-                              const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F,
-                              const uint32_t* pinvB, hipStream_t st) {
-  if constexpr (!E::SHOUP_OUTER) {
-    return hipErrorInvalidValue;
-  } else {
-    hipLaunchKernelGGL((k_build_tw_sh<E>), dim3(grid_1d(count)), dim3(256), 0, st, out, count,
-                       log_r, log_t, log_m, lo, hi, lo_bits, F, pinvB);
-    return hipGetLastError();
-  }
-}
-
-// GZKP rival's `rearrange` (GZKP-NTT.cu:167-233 via reverse pairs), out of place: dst[i] = src[drev(i)].
-// The reference's rounds are radix 2, so its permutation is the bit reversal; here every pass is a
-// natural-order radix-2^r_q DFT, so the permutation that gives natural-order output is the mixed-radix
-// digit reversal: digit q of i (r_q bits, from the low end, in pass order) becomes digit q of the
-// source index counted from the HIGH end.  (All r_q = 1 gives the bit reversal.)
-struct DigitRev {
-  uint32_t nd;
-  uint32_t r[8];
-};
-template <int MEMW>
-__global__ void k_digitrev(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t log_n,
-                           DigitRev D) {
-  NTT_GRID_STRIDE(i, (size_t(1) << log_n)) {
-    size_t j = 0, rem = i;
-    uint32_t top = log_n;
-    for (uint32_t q = 0; q < D.nd; ++q) {
-      top -= D.r[q];
-      j |= (rem & ((1ull << D.r[q]) - 1)) << top;
-      rem >>= D.r[q];
-    }
-    if (D.nd == 0) j = (size_t)(__brevll((unsigned long long)i) >> (64 - log_n));  // log_n 1-bit digits
-    if constexpr (MEMW % 4 == 0) {
-#pragma unroll
-      for (int q = 0; q < MEMW / 4; ++q)
-        reinterpret_cast<uint4*>(dst + i * MEMW)[q] = reinterpret_cast<const uint4*>(src + j * MEMW)[q];
-    } else {
-#pragma unroll
-      for (int q = 0; q < MEMW; ++q) dst[i * MEMW + q] = src[j * MEMW + q];
-    }
-  }
-}
-
-template <class E>
-hipError_t launch_bitrev(const uint32_t* src, uint32_t* dst, uint32_t log_n, const uint32_t* digits, uint32_t nd,
-                         hipStream_t st) {
-  DigitRev D{};
-  uint32_t sum = 0;
-  if (nd > 8 || log_n == 0 || log_n > 40) return hipErrorInvalidValue;
-  D.nd = nd;
-  for (uint32_t q = 0; q < nd; ++q) sum += (D.r[q] = digits[q]);
-  if (nd > 0 && sum != log_n) return hipErrorInvalidValue;  // nd = 0: the bit reversal (digits unused)
-  const size_t n = 1ull << log_n;
-  hipLaunchKernelGGL((k_digitrev<E::MEMW>), dim3(grid_1d(n)), dim3(256), 0, st, src, dst, log_n,
-                     D);
-  return hipGetLastError();
-}
-
-// Four-step twiddle table of one rank (ntt_rplan): entry (a, b) at a 2^log_cols + b holds
-// w_n^((row0 + a)(col0 + b) mod n) R_e (the epilogue of the final pass multiplies by it with mulv),
-// from the two-level tables (lo_s = lo R_e, so lo_s * hi = w R_e).
-template <class E>
-__global__ void k_build_fs_tw(uint32_t* __restrict__ out, uint32_t log_rows, uint32_t log_cols, uint64_t row0,
-                              uint64_t col0, uint32_t log_n, const uint32_t* __restrict__ lo,
-                              const uint32_t* __restrict__ hi, uint32_t lo_bits, const typename E::Args F,
-                              const uint32_t* __restrict__ scale) {
-  NTT_GRID_STRIDE(idx, (size_t(1) << (log_rows + log_cols))) {
-    const uint64_t a = idx >> log_cols, b = idx & ((1ull << log_cols) - 1);
-    const uint64_t e = ((row0 + a) * (col0 + b)) & ((1ull << log_n) - 1);
-    typename E::Tw x, y;
-    E::tload(x, lo, (uint32_t)(e & ((1ull << lo_bits) - 1)));
-    E::tload(y, hi, (uint32_t)(e >> lo_bits));
-    E::mul(x.w, y, F);
-    if (scale) {  // a constant folded into every entry (the four-step's row n2^-1); mul takes any x < B
-      E::tload(y, scale, 0);
-      E::mul(x.w, y, F);
-    }
-    E::template store<E::MUL_OUT, false, E::TABW>(out, idx, x.w, F);
-  }
-}
-
-template <class E>
-hipError_t launch_build_fs_tw(uint32_t* out, uint32_t log_rows, uint32_t log_cols, uint64_t row0, uint64_t col0,
-                              uint32_t log_n, const uint32_t* lo, const uint32_t* hi, uint32_t lo_bits,
-                              const typename E::Args& F, hipStream_t st, const uint32_t* scale) {
-  const size_t count = 1ull << (log_rows + log_cols);
-  hipLaunchKernelGGL((k_build_fs_tw<E>), dim3(grid_1d(count)), dim3(256), 0, st, out, log_rows,
-                     log_cols, row0, col0, log_n, lo, hi, lo_bits, F, scale);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------- four-step helpers
-// Multi-GPU four-step, local steps.  twiddle_pack: src is [rows][row_len] (row-major);
-// element (a, b) is multiplied by w_n^((row0 + a) * b) and written to dst block b / bw (bw =
-// row_len / G) at blk * peer_stride + a * bw + b % bw, i.e. dst = [G][rows][bw] (peer_stride =
-// rows * bw): one contiguous chunk per peer for the all-to-all.  A larger peer_stride interleaves
-// several vectors' chunks per peer (the distributed polymul exchanges a and b in one all-to-all).  Twiddles from the plan's two-level tables: lo_s holds lo * R_e (R_e the engine's
-// Montgomery radix), so t = lo_s[e & mask] * hi[e >> lo_bits] = w_n^e R_e and mulv(x, t) = x w_n^e.
-template <class E>
-__global__ void k_twiddle_pack(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t log_rows,
-                               uint32_t log_len, uint32_t log_bw, uint64_t row0, uint32_t log_n,
-                               const uint32_t* __restrict__ lo, const uint32_t* __restrict__ hi, uint32_t lo_bits,
-                               const typename E::Args F, uint64_t peer_stride) {
-  NTT_GRID_STRIDE(i, (1ull << (log_rows + log_len))) {
-    const uint64_t a = i >> log_len, b = i & ((1ull << log_len) - 1);
-    const uint64_t e = ((row0 + a) * b) & ((1ull << log_n) - 1);
-    uint32_t x[E::W];
-    typename E::Tw w, h;
-    E::load(x, src, i);
-    E::tload(w, lo, (uint32_t)(e & ((1ull << lo_bits) - 1)));
-    E::tload(h, hi, (uint32_t)(e >> lo_bits));
-    E::mul(w.w, h, F);
-    E::mulv(x, w.w, F);
-    const size_t blk = b >> log_bw, off = b & ((1ull << log_bw) - 1);
-    E::template store<E::MUL_OUT>(dst, blk * peer_stride + (a << log_bw) + off, x, F);
-  }
-}
-
-// Coset scale (low-degree-extension step): data[j] *= c^j over `batch` vectors of 2^log_n elements,
-// c^j from two-level tables (lo_s[j & mask] = c^lo R_e, hi[j >> lo_bits] = Shoup entries), so
-// t = lo_s * hi = c^j R_e and mulv(x, t) = x c^j.  One HBM read + write, two products per element.
-template <class E>
-__global__ void k_scale_pow(uint32_t* __restrict__ data, uint32_t log_n, const uint32_t* __restrict__ lo_s,
-                            const uint32_t* __restrict__ hi, uint32_t lo_bits, const typename E::Args F,
-                            size_t batch_stride) {
-  NTT_GRID_STRIDE(j, (size_t(1) << log_n)) {
-    uint32_t* d = data + (size_t)blockIdx.y * batch_stride;
-    uint32_t x[E::W];
-    typename E::Tw w, h;
-    E::load(x, d, j);
-    E::tload(w, lo_s, (uint32_t)(j & ((1ull << lo_bits) - 1)));
-    E::tload(h, hi, (uint32_t)(j >> lo_bits));
-    E::mul(w.w, h, F);
-    E::mulv(x, w.w, F);
-    E::template store<E::MUL_OUT>(d, j, x, F);
-  }
-}
-
-template <class E>
-hipError_t launch_scale_pow(uint32_t* data, uint32_t log_n, uint32_t batch, const uint32_t* lo_s, const uint32_t* hi,
-                            uint32_t lo_bits, const typename E::Args& F, hipStream_t st) {
-  const size_t n = 1ull << log_n;
-  const dim3 grid(grid_1d(n), batch);
-  hipLaunchKernelGGL((k_scale_pow<E>), grid, dim3(256), 0, st, data, log_n, lo_s, hi, lo_bits, F,
-                     n * (size_t)E::MEMW);
-  return hipGetLastError();
-}
-
-// dst[c][r] = src[r][c] for a rows x cols matrix of MEMW-word elements (32x32 tiles through LDS,
-// 16-B vector accesses).  Source rows come in blocks of 2^log_blk_rows rows, block b starting at
-// element b * blk_stride (blk_stride = 2^(log_blk_rows + log_cols): one dense matrix; larger: the
-// per-peer chunks of an all-to-all that carried several vectors).
-template <int MEMW>
-__global__ void k_transpose(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t log_rows,
-                            uint32_t log_cols, uint32_t log_blk_rows, uint64_t blk_stride) {
-  constexpr int TILE = 32;
-  constexpr bool VEC = (MEMW % 4) == 0;
-  __shared__ uint32_t tile[TILE][TILE + 1][MEMW];
-  const uint64_t rows = 1ull << log_rows, cols = 1ull << log_cols;
-  const uint64_t bx = (uint64_t)blockIdx.x * TILE, by = (uint64_t)blockIdx.y * TILE;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 256 threads: 32 x 8
-  for (int k = ty; k < TILE; k += 8) {
-    const uint64_t r = by + k, c = bx + tx;
-    if (r < rows && c < cols) {
-      const uint64_t rin = r & ((1ull << log_blk_rows) - 1);
-      const uint32_t* s = src + ((r >> log_blk_rows) * blk_stride + (rin << log_cols) + c) * MEMW;
-      if constexpr (VEC) {
-#pragma unroll
-        for (int w = 0; w < MEMW / 4; ++w) {
-          const uint4 v = reinterpret_cast<const uint4*>(s)[w];
-          tile[k][tx][4 * w] = v.x;
-          tile[k][tx][4 * w + 1] = v.y;
-          tile[k][tx][4 * w + 2] = v.z;
-          tile[k][tx][4 * w + 3] = v.w;
-        }
-      } else {
-#pragma unroll
-        for (int w = 0; w < MEMW; ++w) tile[k][tx][w] = s[w];
-      }
-    }
-  }
-  __syncthreads();
-  for (int k = ty; k < TILE; k += 8) {
-    const uint64_t c = bx + k, r = by + tx;
-    if (r < rows && c < cols) {
-      uint32_t* d = dst + (c * rows + r) * MEMW;
-      if constexpr (VEC) {
-#pragma unroll
-        for (int w = 0; w < MEMW / 4; ++w)
-          reinterpret_cast<uint4*>(d)[w] =
-              make_uint4(tile[tx][k][4 * w], tile[tx][k][4 * w + 1], tile[tx][k][4 * w + 2], tile[tx][k][4 * w + 3]);
-      } else {
-#pragma unroll
-        for (int w = 0; w < MEMW; ++w) d[w] = tile[tx][k][w];
-      }
-    }
-  }
-}
-
-template <class E>
-hipError_t launch_twiddle_pack(const uint32_t* src, uint32_t* dst, uint32_t log_rows, uint32_t log_len,
-                               uint32_t log_bw, uint64_t row0, uint32_t log_n, const uint32_t* lo, const uint32_t* hi,
-                               uint32_t lo_bits, const typename E::Args& F, uint64_t peer_stride, hipStream_t st) {
-  const size_t total = 1ull << (log_rows + log_len);
-  hipLaunchKernelGGL((k_twiddle_pack<E>), dim3(grid_1d(total)), dim3(256), 0, st, src, dst, log_rows,
-                     log_len, log_bw, row0, log_n, lo, hi, lo_bits, F, peer_stride);
-  return hipGetLastError();
-}
-
-template <class E>
-hipError_t launch_transpose(const uint32_t* src, uint32_t* dst, uint32_t log_rows, uint32_t log_cols,
-                            uint32_t log_blk_rows, uint64_t blk_stride, hipStream_t st) {
-  const uint64_t rows = 1ull << log_rows, cols = 1ull << log_cols;
-  const dim3 grid((uint32_t)((cols + 31) / 32), (uint32_t)((rows + 31) / 32));
-  hipLaunchKernelGGL((k_transpose<E::MEMW>), grid, dim3(256), 0, st, src, dst, log_rows, log_cols, log_blk_rows,
-                     blk_stride);
-  return hipGetLastError();
-}
-
-// In-place digit reversal after an in-place final pass (NTT_PLAN_IN_PLACE; the replacement for the
-// reference's SSIP stage-2 mirror pairs, GZKP-NTT.cu:1359-1449).  With a palindromic radix sequence
-// (R_1 = R_p = 2^R, middle widths symmetric) the element at position (k1, mid, kn) =
-// k1 2^(L-R) + mid 2^R + kn belongs at (kn, midrev, k1): an involution, so the permutation is a set of
-// disjoint swaps.  A workgroup owns the tile pair {(I tb + a, mid, J tb + b)} and its image
-// {(J tb + a, midrev, I tb + b)} (a, b < tb): both tiles are read as tb-element contiguous rows, swapped
-// through LDS and written back transposed.  Of the two workgroups of a pair the one with the larger
-// index exits; a tile that is its own image (mid = midrev, I = J) is transposed in place.
-template <int MW>
-__global__ __launch_bounds__(256) void k_digitrev_swap(uint32_t* data, DrevArgs A) {
-  constexpr int SL = MW + 1;  // LDS slot stride (words): odd, so transposed reads spread over banks
-  __shared__ uint32_t tile[2][256 * SL];
-  const uint32_t tl = A.tb_log, ntl = A.R - tl;
-  const uint64_t u = A.unit0 + blockIdx.x;
-  const uint32_t nm = (1u << ntl) - 1;
-  const uint32_t lo = (uint32_t)(u & nm), hi = (uint32_t)((u >> ntl) & nm);
-  // diagonal order (A.diag): I = lo, J = lo + hi, so that neighbouring workgroups differ in both tile
-  // coordinates and neither tile of a pair walks down one column of 2^(log_n - R)-element rows
-  // (power-of-two strides that land on the same HBM channels); else row-major (I = hi, J = lo)
-  const uint32_t I = A.diag ? lo : hi, J = A.diag ? ((lo + hi) & nm) : lo;
-  const uint64_t mid = u >> (2 * ntl);
-  uint64_t m = mid, midrev = 0;
-  for (uint32_t i = 0; i < A.nmid; ++i) {
-    midrev |= (m & ((1ull << A.mid_bits[i]) - 1)) << A.mid_off[i];
-    m >>= A.mid_bits[i];
-  }
-  // the image tile (midrev, J, I) in the same order
-  const uint64_t partner = (midrev << (2 * ntl)) |
-                           (A.diag ? (((uint64_t)((I - J) & nm) << ntl) | J) : (((uint64_t)J << ntl) | I));
-  if (partner < u) return;  // the pair is handled by the partner's workgroup (uniform exit)
-  uint32_t* d = data + (size_t)blockIdx.y * A.batch_stride;
-  const uint32_t t = threadIdx.x, tb = 1u << tl;
-  const bool act = t < (tb << tl);
-  const uint32_t a = t >> tl, b = t & (tb - 1);
-  const uint32_t sh = A.log_n - A.R;
-  const size_t posA = ((size_t)(I * tb + a) << sh) + (mid << A.R) + J * tb + b;
-  const size_t posB = ((size_t)(J * tb + a) << sh) + (midrev << A.R) + I * tb + b;
-  uint32_t va[MW], vb[MW];
-  if (act) {
-    if constexpr (MW % 4 == 0) {
-#pragma unroll
-      for (int w = 0; w < MW / 4; ++w) {
-        const uint4 x = reinterpret_cast<const uint4*>(d + posA * MW)[w];
-        const uint4 y = reinterpret_cast<const uint4*>(d + posB * MW)[w];
-        va[4 * w] = x.x, va[4 * w + 1] = x.y, va[4 * w + 2] = x.z, va[4 * w + 3] = x.w;
-        vb[4 * w] = y.x, vb[4 * w + 1] = y.y, vb[4 * w + 2] = y.z, vb[4 * w + 3] = y.w;
-      }
-    } else {
-#pragma unroll
-      for (int w = 0; w < MW; ++w) va[w] = d[posA * MW + w], vb[w] = d[posB * MW + w];
-    }
-#pragma unroll
-    for (int w = 0; w < MW; ++w) tile[0][t * SL + w] = va[w], tile[1][t * SL + w] = vb[w];
-  }
-  __syncthreads();
-  if (!act) return;
-  const uint32_t tt = (b << tl) + a;  // the transposed slot
-#pragma unroll
-  for (int w = 0; w < MW; ++w) va[w] = tile[1][tt * SL + w], vb[w] = tile[0][tt * SL + w];
-  const bool self = partner == u;
-  if constexpr (MW % 4 == 0) {
-#pragma unroll
-    for (int w = 0; w < MW / 4; ++w) {
-      reinterpret_cast<uint4*>(d + posA * MW)[w] = make_uint4(va[4 * w], va[4 * w + 1], va[4 * w + 2], va[4 * w + 3]);
-      if (!self)
-        reinterpret_cast<uint4*>(d + posB * MW)[w] = make_uint4(vb[4 * w], vb[4 * w + 1], vb[4 * w + 2], vb[4 * w + 3]);
-    }
-  } else {
-#pragma unroll
-    for (int w = 0; w < MW; ++w) {
-      d[posA * MW + w] = va[w];
-      if (!self) d[posB * MW + w] = vb[w];
-    }
-  }
-}
-
-template <class E>
-hipError_t launch_digitrev_swap(uint32_t* data, const DrevArgs& A, uint32_t batch, hipStream_t st) {
-  if (A.R < A.tb_log || 2 * A.R > A.log_n || A.tb_log > 4) return hipErrorInvalidValue;
-  // grid.x * blockDim.x must stay below 2^32 threads: 2^(log_n - 2 tb_log) tile pairs go as launches
-  // of at most 2^23 workgroups (A.unit0 = the first pair of the launch)
-  const uint64_t units = 1ull << (A.log_n - 2 * A.tb_log), chunk = 1ull << 23;
-  for (uint64_t u0 = 0; u0 < units; u0 += chunk) {
-    DrevArgs B = A;
-    B.unit0 = u0;
-    const uint64_t cnt = units - u0 < chunk ? units - u0 : chunk;
-    hipLaunchKernelGGL((k_digitrev_swap<E::MEMW>), dim3((uint32_t)cnt, batch), dim3(256), 0, st, data, B);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// ---------------------------------------------------------------------------- utility kernels
-__device__ __forceinline__ uint64_t splitmix64(uint64_t c) {
-  uint64_t z = c + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// SURVEY §8d vector B: limb_i = SplitMix64(seed*2^32 + 4j + i) (64-bit limbs), limbs at and above
-// `nrand` zero, the top random limb masked to `top_bits` so that every value is < p.
-struct FillMap {
-  uint64_t row0;       // global index of local row 0
-  uint32_t log_inner;  // local row length (log2); 64 = identity map
-  uint32_t log_stride; // global stride of the inner index (log2)
-};
-__device__ __forceinline__ uint64_t fill_index(size_t i, const FillMap& m) {
-  if (m.log_inner >= 64) return i;
-  return m.row0 + (i >> m.log_inner) + ((uint64_t)(i & ((1ull << m.log_inner) - 1)) << m.log_stride);
-}
-
-template <int MEMW>
-__global__ void k_fill_random(uint32_t* __restrict__ dst, size_t n, uint64_t seed, uint32_t nrand, uint32_t top_bits,
-                              FillMap fm) {
-  NTT_GRID_STRIDE(i, n) {
-    const uint64_t j = fill_index(i, fm);
-    if constexpr (MEMW == 1) {  // 4-B elements: the low limb's draw masked below 2^31 (top_bits <= 30)
-      dst[i] = (uint32_t)(splitmix64((seed << 32) + 4 * j) & ((1ull << top_bits) - 1));
-    } else if constexpr (MEMW == 2) {
-      const uint64_t v = splitmix64((seed << 32) + 4 * j) & ((1ull << top_bits) - 1);
-      reinterpret_cast<uint2*>(dst)[i] = make_uint2((uint32_t)v, (uint32_t)(v >> 32));  // P: top_bits < 32
-    } else {
-      uint32_t v[MEMW];
-#pragma unroll
-      for (int l = 0; l < MEMW / 2; ++l) {
-        uint64_t limb = 0;
-        if ((uint32_t)l < nrand) {
-          limb = splitmix64((seed << 32) + 4 * j + l);
-          if ((uint32_t)l + 1 == nrand && top_bits < 64) limb &= (1ull << top_bits) - 1;
-        }
-        v[2 * l] = (uint32_t)limb;
-        v[2 * l + 1] = (uint32_t)(limb >> 32);
-      }
-      uint4* p = reinterpret_cast<uint4*>(dst + i * MEMW);
-#pragma unroll
-      for (int q = 0; q < MEMW / 4; ++q) p[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    }
-  }
-}
-
-template <int MEMW>
-__global__ void k_fill_iota(uint32_t* __restrict__ dst, size_t n, FillMap fm) {
-  NTT_GRID_STRIDE(i, n) {
-    const uint64_t j = fill_index(i, fm);
-    if constexpr (MEMW == 1) {  // 4-B elements: the index's low word (plans of at most 2^27 points)
-      dst[i] = (uint32_t)j;
-    } else if constexpr (MEMW == 2) {
-      reinterpret_cast<uint2*>(dst)[i] = make_uint2((uint32_t)j, (uint32_t)((uint64_t)j >> 32));
-    } else {
-      uint4* p = reinterpret_cast<uint4*>(dst + i * MEMW);
-      p[0] = make_uint4((uint32_t)j, (uint32_t)((uint64_t)j >> 32), 0u, 0u);
-#pragma unroll
-      for (int q = 1; q < MEMW / 4; ++q) p[q] = make_uint4(0u, 0u, 0u, 0u);
-    }
-  }
-}
-
-template <class E>
-__global__ void k_pointwise_mul(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ c,
-                                size_t n, const typename E::Args F, const uint32_t* __restrict__ r2, const FsMap m,
-                                const uint32_t mapped) {
-  NTT_GRID_STRIDE(j, n) {
-    uint32_t x[E::W], y[E::W];
-    typename E::Tw z;  // R_e mod p as a twiddle: mulv leaves x y / R_e
-    const size_t src = mapped ? m(j, 0) : j;  // a four-step piece gathered from the column layout
-    E::load(x, a, src);
-    E::load(y, b, src);
-    E::tload(z, r2, 0);
-    E::mulv(x, y, F);
-    E::mul(x, z, F);
-    E::template store<E::MUL_OUT>(c, j, x, F);
-  }
-}
-
-// Canonical-range check (the reference's padded-store `BAD LIMB` trap, impl_cuda.cu:1402-1408, as a
-// query): counts elements that are not < p in a caller buffer of E::MEMW-word elements.  p holds
-// the modulus in MEMW little-endian 32-bit words (zero above its top word).
-template <int MEMW>
-__global__ void k_count_noncanonical(const uint32_t* __restrict__ d, size_t n, ModWords<MEMW> p,
-                                     unsigned long long* __restrict__ bad) {
-  NTT_GRID_STRIDE(i, n) {
-    const uint32_t* e = d + i * MEMW;
-    int cmp = 0;  // sign of e - p, decided by the most significant differing word
-#pragma unroll
-    for (int k = MEMW - 1; k >= 0; --k)
-      if (cmp == 0 && e[k] != p.w[k]) cmp = e[k] < p.w[k] ? -1 : 1;
-    if (cmp >= 0) atomicAdd(bad, 1ull);
-  }
-}
-
-template <class E>
-hipError_t launch_count_noncanonical(const uint32_t* d, size_t n, const ModWords<E::MEMW>& p,
-                                     unsigned long long* bad, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL((k_count_noncanonical<E::MEMW>), dim3(grid_1d(n)), dim3(256), 0, st, d, n, p,
-                     bad);
-  return hipGetLastError();
-}
-
 // ---------------------------------------------------------------------------- launchers
 // Radices the planner can emit: column/final passes use 3 <= r <= tile_log - MIN_COLS_LOG, single-workgroup
 // transforms 3 <= r <= tile_log.  Only those are instantiated.
@@ -1896,115 +1074,6 @@ hipError_t launch_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, c
   return launch_pass_kind<E, KIND_SINGLE>(logr, src, dst, A, grid, batch, st);
 }
 
-// The PRO_LDE pass (low-degree extension, ntt_lde_batch): one outer-table form per engine.  Fast-
-// reduction engines on a modulus that takes them (A.F.red_ok) run the column pass with the shift's
-// full table (A.tw_full and A.tw_in, as PRO_COSET) and KIND_SINGLE in the FAST form; every other case
-// the generic reductions with two-level outer twiddles.
-template <class E, int KIND, int LOGR>
-static hipError_t launch_lde_r(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid, uint32_t batch,
-                               hipStream_t st) {
-  constexpr int TL = tile_log_of<E>();
-  constexpr int MAXR = (KIND == KIND_SINGLE) ? TL : TL - E::MIN_COLS_LOG;
-  if constexpr (LOGR > MAXR || !HasLde<E>::value) {
-    return hipErrorInvalidValue;
-  } else {
-    constexpr int TE = (KIND == KIND_SINGLE) ? (1 << LOGR) : (1 << TL);
-    constexpr int NT = TE / E::EPT;
-    const dim3 g(grid, batch), b(NT < 64 ? 64 : NT);
-    if (A.fs || A.tw_epi || A.src2 || A.tw_sh || A.src_stride == 0) return hipErrorInvalidValue;
-    if constexpr (E::FASTRED) {
-      if (A.F.red_ok) {
-        // a plan's passes are all FAST or all generic: no generic column pass beside FAST later ones
-        // (a FAST plan without full tables takes the staging route instead)
-        if constexpr (KIND == KIND_COLUMN) {
-          if (!A.tw_full) return hipErrorInvalidValue;
-          hipLaunchKernelGGL((k_pass<E, LOGR, KIND_COLUMN, true, true, PRO_LDE>), g, b, 0, st, src, dst, A);
-        } else {
-          hipLaunchKernelGGL((k_pass<E, LOGR, KIND_SINGLE, false, true, PRO_LDE>), g, b, 0, st, src, dst, A);
-        }
-        return hipGetLastError();
-      }
-    }
-    if (A.tw_full || (A.tw_in && !lde_mul_at_load<E, KIND>())) return hipErrorInvalidValue;
-    if constexpr (!lde_pass_available<E>(KIND, LOGR, false)) {
-      return hipErrorInvalidValue;
-    } else {
-      hipLaunchKernelGGL((k_pass<E, LOGR, KIND, false, false, PRO_LDE>), g, b, 0, st, src, dst, A);
-      return hipGetLastError();
-    }
-  }
-}
-
-template <class E, int KIND>
-static hipError_t launch_lde_kind(int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
-                                  uint32_t batch, hipStream_t st) {
-  return with_radix<3, 13>(logr, [&](auto R) { return launch_lde_r<E, KIND, R>(src, dst, A, grid, batch, st); });
-}
-
-// The inputs of a low-degree extension times c^j, into a staging buffer of the same layout
-// (launch_lde_scale, ntt_kernels.hpp); input v is blockIdx.y
-template <class E>
-__global__ void k_lde_scale(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t n_in,
-                            const uint32_t* __restrict__ lo_s, const uint32_t* __restrict__ hi, uint32_t lo_bits,
-                            const typename E::Args F) {
-  NTT_GRID_STRIDE(j, n_in) {
-    const size_t i = (size_t)blockIdx.y * n_in + j;
-    uint32_t x[E::W];
-    typename E::Tw w, h;
-    E::load(x, src, i);
-#if NTT_DEBUG_CHECKS
-    if (!E::dbg_canonical(x, F)) ntt_dbg_flag(F.dbg, NTT_DBG_INPUT);
-#endif
-    E::tload(w, lo_s, (uint32_t)(j & ((1ull << lo_bits) - 1)));
-    E::tload(h, hi, (uint32_t)(j >> lo_bits));
-    E::mul(w.w, h, F);
-    E::mulv(x, w.w, F);
-    E::template store<E::MUL_OUT>(dst, i, x, F);
-  }
-}
-
-template <class E>
-hipError_t launch_lde_scale(const uint32_t* src, uint32_t* dst, size_t n_in, uint32_t batch, const uint32_t* lo_s,
-                            const uint32_t* hi, uint32_t lo_bits, const typename E::Args& F, hipStream_t st) {
-  hipLaunchKernelGGL((k_lde_scale<E>), dim3(grid_1d(n_in), batch), dim3(256), 0, st, src, dst, n_in, lo_s, hi, lo_bits, F);
-  return hipGetLastError();
-}
-
-template <class E>
-hipError_t launch_lde_pass(int kind, int logr, const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t grid,
-                           uint32_t batch, hipStream_t st) {
-  if (kind == KIND_COLUMN) return launch_lde_kind<E, KIND_COLUMN>(logr, src, dst, A, grid, batch, st);
-  if (kind == KIND_SINGLE) return launch_lde_kind<E, KIND_SINGLE>(logr, src, dst, A, grid, batch, st);
-  return hipErrorInvalidValue;
-}
-
-template <class E>
-hipError_t launch_naive(const uint32_t* src, uint32_t* dst, const PassArgs<E>& A, uint32_t batch, hipStream_t st) {
-  hipLaunchKernelGGL((k_dft_naive<E>), dim3(1, batch), dim3(64), 0, st, src, dst, A);
-  return hipGetLastError();
-}
-
-template <class E>
-hipError_t launch_fill(int kind, uint32_t* dst, size_t n, uint64_t seed, uint32_t nrand, uint32_t top_bits,
-                       uint64_t row0, uint32_t log_inner, uint32_t log_stride, hipStream_t st) {
-  const uint32_t blocks = grid_1d(n);
-  const FillMap fm{row0, log_inner, log_stride};
-  if (kind == 0)
-    hipLaunchKernelGGL((k_fill_iota<E::MEMW>), dim3(blocks), dim3(256), 0, st, dst, n, fm);
-  else
-    hipLaunchKernelGGL((k_fill_random<E::MEMW>), dim3(blocks), dim3(256), 0, st, dst, n, seed, nrand, top_bits, fm);
-  return hipGetLastError();
-}
-
-template <class E>
-hipError_t launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* c, size_t n, const typename E::Args& F,
-                            const uint32_t* d_r2, hipStream_t st, const FsMap* in_map) {
-  const uint32_t blocks = grid_1d(n);
-  const FsMap m = in_map ? *in_map : FsMap{};
-  hipLaunchKernelGGL((k_pointwise_mul<E>), dim3(blocks), dim3(256), 0, st, a, b, c, n, F, d_r2, m, in_map ? 1u : 0u);
-  return hipGetLastError();
-}
-
 // One pass kind of one engine per translation unit (the kernels dominate compile time).
 #define NTT_INSTANTIATE_KIND(E, KIND)                                                                          \
   template hipError_t launch_pass_kind<E, KIND>(int, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
@@ -2014,13 +1083,7 @@ hipError_t launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* c, s
   extern template hipError_t launch_pass_kind<E, KIND>(int, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
                                                        uint32_t, hipStream_t);
 
-// The PRO_LDE passes of one engine (a translation unit of their own: ntt_*_lde.hip)
-#define NTT_INSTANTIATE_LDE(E)                                                                                  \
-  template hipError_t launch_lde_pass<E>(int, int, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, \
-                                         uint32_t, hipStream_t);                                             \
-  template hipError_t launch_lde_scale<E>(const uint32_t*, uint32_t*, size_t, uint32_t, const uint32_t*,       \
-                                          const uint32_t*, uint32_t, const typename E::Args&, hipStream_t);
-
+// The pass-level dispatch of one engine (ntt_*_misc.hip): the kinds live in units of their own
 #define NTT_INSTANTIATE(E)                                                                                         \
   NTT_EXTERN_KIND(E, KIND_COLUMN)                                                                                  \
   NTT_EXTERN_KIND(E, KIND_FINAL)                                                                                   \
@@ -2028,42 +1091,6 @@ hipError_t launch_pointwise(const uint32_t* a, const uint32_t* b, uint32_t* c, s
   NTT_EXTERN_KIND(E, KIND_STOCKHAM)                                                                                \
   NTT_EXTERN_KIND(E, KIND_DIT)                                                                                     \
   template hipError_t launch_pass<E>(int, int, const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, uint32_t, \
-                                     hipStream_t);                                                                 \
-  template hipError_t launch_naive<E>(const uint32_t*, uint32_t*, const PassArgs<E>&, uint32_t, hipStream_t);       \
-  template hipError_t launch_fill<E>(int, uint32_t*, size_t, uint64_t, uint32_t, uint32_t, uint64_t, uint32_t,     \
-                                     uint32_t, hipStream_t);                                                       \
-  template hipError_t launch_twiddle_pack<E>(const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, uint64_t,   \
-                                             uint32_t, const uint32_t*, const uint32_t*, uint32_t,                 \
-                                             const typename E::Args&, uint64_t, hipStream_t);                      \
-  template hipError_t launch_transpose<E>(const uint32_t*, uint32_t*, uint32_t, uint32_t, uint32_t, uint64_t,     \
-                                          hipStream_t);                                                            \
-  template hipError_t launch_digitrev_swap<E>(uint32_t*, const DrevArgs&, uint32_t, hipStream_t);                  \
-  template hipError_t launch_final_ipn<E>(int, uint32_t*, const PassArgs<E>&, uint32_t, hipStream_t);              \
-  template uint32_t launch_final_ipn_capacity<E>(int, int);                                                        \
-  template hipError_t launch_pointwise<E>(const uint32_t*, const uint32_t*, uint32_t*, size_t,                     \
-                                          const typename E::Args&, const uint32_t*, hipStream_t, const FsMap*);    \
-  template hipError_t launch_build_tw<E>(uint32_t*, size_t, uint32_t, uint32_t, uint32_t, const uint32_t*,        \
-                                         const uint32_t*, uint32_t, const typename E::Args&, hipStream_t,          \
-                                         const uint32_t*, const uint32_t*);                                        \
-  template hipError_t launch_bitrev<E>(const uint32_t*, uint32_t*, uint32_t, const uint32_t*, uint32_t,           \
-                                       hipStream_t);                                                              \
-  template hipError_t launch_build_tw_sh<E>(uint32_t*, size_t, uint32_t, uint32_t, uint32_t, const uint32_t*,     \
-                                            const uint32_t*, uint32_t, const typename E::Args&, const uint32_t*,  \
-                                            hipStream_t);                                                         \
-  template hipError_t launch_build_fs_tw<E>(uint32_t*, uint32_t, uint32_t, uint64_t, uint64_t, uint32_t,           \
-                                            const uint32_t*, const uint32_t*, uint32_t, const typename E::Args&,    \
-                                            hipStream_t, const uint32_t*);                                                           \
-  template hipError_t launch_scale_pow<E>(uint32_t*, uint32_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t, \
-                                          const typename E::Args&, hipStream_t);                                   \
-  template hipError_t launch_count_noncanonical<E>(const uint32_t*, size_t, const ModWords<E::MEMW>&,              \
-                                                   unsigned long long*, hipStream_t);                              \
-  template hipError_t launch_build_pow<E>(uint32_t*, size_t, const uint32_t*, const uint32_t*, uint32_t,           \
-                                          const typename E::Args&, hipStream_t);                                   \
-  template hipError_t launch_naive_round<E>(const uint32_t*, uint32_t*, uint32_t, uint32_t, const uint32_t*,       \
-                                            const typename E::Args&, hipStream_t);                                 \
-  template hipError_t launch_noswap_round<E>(const uint32_t*, uint32_t*, uint32_t, uint32_t, const uint32_t*,      \
-                                             const typename E::Args&, hipStream_t);                                 \
-  template hipError_t launch_bealto<E>(int, const uint32_t*, uint32_t*, const PassArgs<E>&, const BealtoArgs&,     \
-                                       hipStream_t);
+                                     hipStream_t);
 
 }  // namespace ntt

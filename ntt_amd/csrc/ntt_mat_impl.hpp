@@ -2,6 +2,7 @@
 // strip form of the pass tile (pass_tile's MAT option, ntt_kernels_impl.hpp), and k_mat_naive for 2 and 4
 // rows.  Included by ntt_eg_mat.hip and ntt_e31_mat.hip alone.
 #pragma once
+#include "ntt_elementwise_impl.hpp"  // grid_1d, NTT_GRID_STRIDE (k_mat_naive)
 #include "ntt_kernels_impl.hpp"
 
 namespace ntt {

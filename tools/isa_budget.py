@@ -27,7 +27,7 @@ CATEGORIES = [
     (r"^(reduce_top|reduce|reduce_chain|cond_sub|cond_sub_rare|store_lazy|store)$", "reductions (quotient estimate, conditional subtractions)"),
     (r"^(pack29|unpack29|load|put|store_wt16)$", "HBM format: pack29 / unpack29 + vector loads/stores"),
     (r"^(tload|twiddle_mul|twiddle_mul_lds|mul|mul_u|mulv)$", "twiddle-table loads and product call glue"),
-    (r"^(lds_put_part|lds_get_part|lds_slot)$", "LDS exchange (slot addressing, ds_read/ds_write)"),
+    (r"^(lds_put|lds_get|lds_slot)$", "LDS exchange (slot addressing, ds_read/ds_write)"),
     (r"^(substage|sub_map|natural_index|pass_tile|k_pass|brev_bits|static_for|static_for_impl|operator\(\))$",
      "tile addressing and control (positions, group maps, branches)"),
 ]

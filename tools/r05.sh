@@ -81,11 +81,6 @@ for s in $ARGS; do
       step pmc_sq 120 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU GRBM_GUI_ACTIVE -d $O/pmc/sq -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --prewarm-s 0
       step pmc_fetch 120 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc/fetch -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --prewarm-s 0
       step pmc_write 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc/write -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --prewarm-s 0 ;;
-    # the exit-time SIGSEGV of cooperative launches under rocprofv3: the probe
-    # dumps /proc/self/maps at Python exit; tools/symbolize_trace.py resolves the trace.  probe_coop is
-    # expected to crash at exit: run it LAST in a call.
-    probe_plain) step probe_plain 200 rocprofv3 --kernel-trace --stats -d $O/probe_plain -o run --output-format csv -- python3 tools/exit_crash_probe.py $O/maps_plain.txt --coop 0 ;;
-    probe_coop) step probe_coop 200 rocprofv3 --kernel-trace --stats -d $O/probe_coop -o run --output-format csv -- python3 tools/exit_crash_probe.py $O/maps_coop.txt --coop 1 ;;
     *) echo "unknown step $s" >&2; exit 2 ;;
   esac
 done

@@ -1,5 +1,5 @@
 """Resolve a glog-style crash trace ("    @     0x7581f148d59e (unknown)") against a /proc/<pid>/maps
-dump of the same process (tools/exit_crash_probe.py) into library + offset, then into function names
+dump of the same process (profiles/r05_exitcrash/ holds one) into library + offset, then into function names
 with llvm-symbolizer (the libraries are the same image's, so they can be read here).
 
     python tools/symbolize_trace.py CRASH_LOG MAPS [--json out.json]
