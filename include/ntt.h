@@ -354,6 +354,62 @@ int ntt_fri_fold(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_row
                  unsigned ext_degree, uint64_t ext_w, const uint64_t* beta, const uint64_t* shift,
                  void* hip_stream);
 
+/* DEEP openings and quotients of a row-major coset evaluation matrix: what lies between
+ * ntt_lde_matrix_ex(..., NTT_MATRIX_BITREV_OUT) and ntt_fri_fold.
+ * With L = log_rows (0 <= L <= the plan's log_n), N = 2^L, w_N = w_n^(n/N) from the plan's root, c = *shift
+ * (1 when NULL), sigma the identity when order == 0 and rev_L when order == NTT_MATRIX_BITREV_OUT, and
+ * x_i = c w_N^sigma(i): M = d_mat = [N][width] holds base-field rows, column j the evaluations p_j(x_i) of a
+ * polynomial of degree < N.  An extension element is d = ext_degree in {1, 2, 4} adjacent base coefficients of
+ * F_p[X]/(X^d - W), W = ext_w, as in ntt_fri_fold.  M, d_values and d_out are in the plan's I/O form
+ * (Montgomery on NTT_PLAN_MONTGOMERY_IO plans); the host words z, alpha, scale, ext_w and shift are always
+ * canonical.
+ *   ntt_deep_points  d_inv [N][d]: d_inv[i] = (z - x_i)^-1 in the WORKING FORM: on the 4-byte engines the value
+ *     times 2^32 mod p, for every plan kind; on Goldilocks the plain value.  (A Montgomery product of such a
+ *     value with a datum in either I/O form is the plain product in the datum's form; ntt_fri_fold holds its
+ *     t R the same way.)  x_i comes from the plan's two-level tables at stride 2^(log_n - log_rows): no table
+ *     is built.  Each thread inverts a run of 16 / d (4-byte engines; 8 / d on Goldilocks) consecutive rows with
+ *     one extension inversion (Montgomery's batch trick).  NTT_ERR_ARG before any launch when z lies in the
+ *     base field (d = 1, or coordinates 1.. all zero) and z_0^N = c^N: the only case in which z hits the
+ *     domain.  Where X^d - W is reducible and some z - x_i is not invertible, the rows of that run are
+ *     unspecified; nothing faults.
+ *   ntt_matrix_open  d_values [width][d]: d_values[j] = p_j(z), by the barycentric form
+ *     p_j(z) = (z^N - c^N) / (N c^N) sum_i M[i][j] x_i / (z - x_i), with x_i / (z - x_i) = z / (z - x_i) - 1: two
+ *     sums over the rows, sum_i M[i][j] d_inv[i] and sum_i M[i][j].  d_inv is ntt_deep_points' output for the
+ *     same log_rows, ext_degree, ext_w, z, shift and order.  Two launches: strips of columns x chunks of rows into
+ *     a plan-owned buffer (allocated at the first use, its size independent of N), then the chunks in order
+ *     and the two host-computed scalars.  No atomics: the same bits every run.  The base-field z of the coset
+ *     is NTT_ERR_ARG here too.
+ *   ntt_deep_quotient  d_out [N][d]:
+ *       d_out[i] = scale d_inv[i] (sum_j alpha^j v_j - sum_j alpha^j M[i][j]),  v_j = d_values[j],
+ *     which is scale sum_j alpha^j (p_j(x_i) - v_j) / (x_i - z).  scale == NULL is 1.  flags &
+ *     NTT_DEEP_ACCUMULATE adds into d_out (its elements canonical in the plan's form), so several opening
+ *     points or matrices sum into one codeword, with scale = alpha^width for the second.  The row order lives
+ *     in d_inv.  Two launches: the table scale alpha^j (each entry by square and multiply) and
+ *     V = scale sum_j alpha^j v_j into the plan-owned buffer, then the rows: 2^k lanes share a row and stride its
+ *     columns, 2^k a quarter of the largest power of two up to the width, at least 64 bytes of lanes (16 on
+ *     4-byte elements, 8 on 8-byte ones) and at most 64; rows shorter than 64 bytes take one lane per row, each
+ *     lane several rows in turn and each wave reading 64 consecutive rows at a time.
+ *   ntt_deep_info  the two shape decisions at (width, log_rows, ext_degree): the row chunks of ntt_matrix_open
+ *     and the lanes per row of ntt_deep_quotient.  No launch.
+ * The three launching calls are asynchronous on hip_stream and never synchronise the host.  Any
+ * element-aligned pointer is accepted; 16-byte accesses are used when the pointers are 16-byte aligned.
+ * Engines: as the matrix calls; plans of fields 0-2 and of custom 4- and 6-limb moduli return NTT_ERR_ARG.
+ * NTT_ERR_ARG before any launch, the buffers untouched: a null plan or pointer (shift and scale may be NULL),
+ * width 0, N width >= 2^32, log_rows above the plan's log_n, ext_degree outside {1, 2, 4}, ext_w 0 or >= p when
+ * ext_degree > 1 (ignored at 1), a z, alpha, scale or shift word >= p, a zero shift, an unknown bit in order
+ * or flags, NTT_PLAN_TWIDDLE_ONLY plans, overlapping byte ranges of an output with any input. */
+#define NTT_DEEP_ACCUMULATE 1u
+int ntt_deep_points(ntt_plan* plan, void* d_inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w,
+                    const uint64_t* z, const uint64_t* shift, unsigned order, void* hip_stream);
+int ntt_matrix_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_inv,
+                    unsigned ext_degree, uint64_t ext_w, const uint64_t* z, const uint64_t* shift, unsigned order,
+                    void* d_values, void* hip_stream);
+int ntt_deep_quotient(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_inv,
+                      const void* d_values, unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha,
+                      const uint64_t* scale, unsigned flags, void* d_out, void* hip_stream);
+int ntt_deep_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned ext_degree,
+                  unsigned* open_row_chunks, unsigned* quotient_lanes_per_row);
+
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */
 int ntt_pointwise_mul(ntt_plan* plan, const void* d_a, const void* d_b, void* d_c, void* hip_stream);
@@ -413,8 +469,9 @@ int ntt_plan_last_launch_ms(ntt_plan* plan, float* ms, unsigned max_launches, un
 /* The same launches' labels, comma-separated, in launch order: a kind letter and the pass's log2
  * radix (c column pass, "s" appended when it reads a Shoup-pair outer table; f final pass; s one
  * transform per workgroup; r several per workgroup; i in-place final pass with the digit reversal;
- * d digit-reversal swap; b single launch; n naive; x FRI fold, with log_arity for the radix), "" when
- * unlabelled.  NTT_ERR_ARG when `cap`
+ * d digit-reversal swap; b single launch; n naive; x FRI fold, with log_arity for the radix; z DEEP points;
+ * o open: strip sums, e open: the chunks and the scalars; a quotient: the alpha table, q quotient: the rows), ""
+ * when unlabelled.  NTT_ERR_ARG when `cap`
  * bytes do not hold them.  New (round 6): benchmarks pair per-launch PMC bytes with launches by
  * label, not by position. */
 int ntt_plan_last_launch_labels(ntt_plan* plan, char* buf, unsigned cap);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "engines.hpp"
+#include "fieldext.hpp"
 #include "plan_fused.hpp"
 
 namespace ntt {
@@ -359,6 +360,104 @@ struct FoldArgs {
 template <class E>
 hipError_t launch_fri_fold(unsigned log_arity, unsigned ext_degree, bool staged, const uint32_t* in, uint32_t* out,
                            const FoldArgs<E>& A, hipStream_t st);
+
+// ---- DEEP openings and quotients of a row-major coset evaluation matrix (ntt_deep_points, ntt_matrix_open,
+// ntt_deep_quotient; kernels in ntt_deep_impl.hpp, instances in ntt_eg_deep.hip and ntt_e31_deep.hip: the HasMat
+// engines).  Host scalars travel in the kernel arguments in the field's working form
+// (fieldext.hpp xf: v 2^32 mod p on Eng31, the value on Eng64G).
+template <class E>
+using deep_val_t = std::conditional_t<std::is_same_v<E, Eng31>, uint32_t, uint64_t>;
+template <class E>
+using deep_k_t = std::conditional_t<std::is_same_v<E, Eng31>, xf::K31, xf::K64>;
+// The shape decisions, shared by the launchers, the kernels and ntt_deep_info.  memw = E::MEMW.
+struct DeepShape {
+  static constexpr unsigned BT = 256;          // threads of every DEEP workgroup
+  static constexpr unsigned RUN_WORDS = 16;    // points: each thread owns 64 B of consecutive output rows
+  static constexpr unsigned UNROLL = 4;        // open: rows a thread has in flight
+  static constexpr unsigned TARGET_WGS = 2048; // open: workgroups wanted (256 CUs x 8)
+  static constexpr unsigned MAX_CHUNKS = 1024; // open: row chunks at most, whatever N
+  static constexpr unsigned FIN_COLS = 16;     // open, second launch: columns per workgroup (x BT / 16 chunk lanes)
+  static constexpr unsigned TAB_COLS = 512;    // quotient: columns of the scale alpha^j table held in LDS
+  static constexpr unsigned SCR_TAB = 4;       // quotient scratch: V in elements [0, d), the table from element 4
+  __host__ __device__ static constexpr unsigned ceil_log2(unsigned v) {
+    unsigned l = 0;
+    while (l < 32 && (1ull << l) < v) ++l;
+    return l;
+  }
+  // open: log2 of a strip's columns: the width rounded up to a power of two, at least 64 B per row, at most a wave
+  __host__ __device__ static constexpr unsigned strip_log(unsigned width, int memw) {
+    const unsigned lo = memw == 1 ? 4u : 3u, l = ceil_log2(width);
+    return l < lo ? lo : (l > 6 ? 6u : l);
+  }
+  __host__ __device__ static constexpr unsigned strips(unsigned width, int memw) {
+    const unsigned l = strip_log(width, memw);
+    return (unsigned)(((uint64_t)width + (1u << l) - 1) >> l);
+  }
+  // open: rows per chunk (a multiple of the rows one workgroup step covers); the chunks are ceil(N / that):
+  // enough of them for TARGET_WGS workgroups, at most MAX_CHUNKS, none empty
+  __host__ __device__ static constexpr uint64_t open_chunk_rows(unsigned width, unsigned log_rows, int memw) {
+    const uint64_t n = 1ull << log_rows, step = (uint64_t)(BT >> strip_log(width, memw)) * UNROLL;
+    const unsigned ns = strips(width, memw);
+    uint64_t want = (TARGET_WGS + ns - 1) / ns;
+    if (want > MAX_CHUNKS) want = MAX_CHUNKS;
+    if (want < 1) want = 1;
+    const uint64_t rows = (n + want - 1) / want;
+    return (rows + step - 1) / step * step;
+  }
+  __host__ __device__ static constexpr unsigned open_chunks(unsigned width, unsigned log_rows, int memw) {
+    const uint64_t n = 1ull << log_rows, cr = open_chunk_rows(width, log_rows, memw);
+    return (unsigned)((n + cr - 1) / cr);
+  }
+  // quotient: log2 of the lanes that share a row.  Rows shorter than 64 B: one lane per row (a wave then reads
+  // 64 consecutive rows, one contiguous run); otherwise a quarter of the largest power of two up to the width
+  // (four columns a lane: the cross-lane sum is paid once per row, whatever the lane's share), 64 B of lanes at
+  // least (16 on 4-byte elements, 8 on 8-byte ones), a wave at most
+  __host__ __device__ static constexpr unsigned lanes_log(unsigned width, int memw) {
+    if ((uint64_t)width * 4 * memw < 64) return 0;
+    const unsigned lo = memw == 1 ? 4u : 3u;
+    unsigned l = 0;
+    while (l < 8 && (2u << l) <= width) ++l;
+    l = l >= 2 ? l - 2 : 0;
+    return l < lo ? lo : (l > 6 ? 6u : l);
+  }
+};
+template <class E>
+struct DeepArgs {
+  typename E::Args F;  // p, p^-1, the checked build's status word
+  deep_k_t<E> K;       // the field's constants with W
+  uint32_t log_rows, width;
+  uint32_t vec;    // the call's row buffers are 16-byte aligned and whole 16-byte words long: vector access
+  uint32_t flags;  // quotient: NTT_DEEP_ACCUMULATE
+  size_t mat_elems, inv_elems, val_elems, out_elems, scr_elems;  // checked build: elements of each buffer
+  // points: x_i = c w_n^(sigma(i) << tab_shift) from the forward two-level tables (lo scaled by R_e, plain hi)
+  const uint32_t* lo_s;
+  const uint32_t* hi;
+  uint32_t lo_bits, tab_shift, bitrev;
+  typename E::Tw c;
+  deep_val_t<E> z[4];  // z (points and the open's second launch)
+  // open
+  uint32_t strip_log, chunks;
+  uint64_t chunk_rows;
+  deep_val_t<E> k[4];  // (z^N - c^N) / (N c^N)
+  // quotient
+  uint32_t lanes_log;
+  deep_val_t<E> alpha[4], scale[4];
+};
+// ext_degree 1, 2 or 4 in each.  points: d_inv [N][d].  open: mat [N][width], inv -> part (chunks (d + 1) width
+// elements of plan scratch), then part -> values [width][d].  quotient: values -> scr (SCR_TAB + width d
+// elements of plan scratch), then mat, inv, scr -> out [N][d].
+template <class E>
+hipError_t launch_deep_points(unsigned d, uint32_t* inv, const DeepArgs<E>& A, hipStream_t st);
+template <class E>
+hipError_t launch_deep_open(unsigned d, const uint32_t* mat, const uint32_t* inv, uint32_t* part, const DeepArgs<E>& A,
+                            hipStream_t st);
+template <class E>
+hipError_t launch_deep_open_fin(unsigned d, const uint32_t* part, uint32_t* values, const DeepArgs<E>& A, hipStream_t st);
+template <class E>
+hipError_t launch_deep_qpro(unsigned d, const uint32_t* values, uint32_t* scr, const DeepArgs<E>& A, hipStream_t st);
+template <class E>
+hipError_t launch_deep_quotient(unsigned d, const uint32_t* mat, const uint32_t* inv, const uint32_t* scr, uint32_t* out,
+                                const DeepArgs<E>& A, hipStream_t st);
 
 template <class E>
 hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,

@@ -88,6 +88,7 @@ struct FirstPass {
 }  // namespace
 
 // the plan's features, each a struct the plan owns and hands a reference to itself; they name FirstPass
+#include "plan_deep.hpp"    // Deep<E, Plan>: DEEP openings and quotients of evaluation matrices
 #include "plan_fold.hpp"    // Fold<E, Plan>: ntt_fri_fold
 #include "plan_matrix.hpp"  // Matrix<E, Plan>: the row-major matrix transforms
 #include "plan_rivals.hpp"  // Rivals<E, Plan>: the rival schedules
@@ -140,6 +141,18 @@ struct PlanBase {
   // FRI fold of bit-reversed coset evaluations (ntt_fri_fold): [2^log_rows][d] -> [2^(log_rows - log_arity)][d]
   virtual int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree,
                    uint64_t ext_w, const uint64_t* beta, const uint64_t* shift, hipStream_t st) = 0;
+  // DEEP openings and quotients of a row-major coset evaluation matrix (ntt_deep_points, ntt_matrix_open,
+  // ntt_deep_quotient, ntt_deep_info)
+  virtual int deep_points(void* inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w, const uint64_t* z,
+                          const uint64_t* shift, unsigned order, hipStream_t st) = 0;
+  virtual int deep_open(const void* mat, unsigned width, unsigned log_rows, const void* inv, unsigned ext_degree,
+                        uint64_t ext_w, const uint64_t* z, const uint64_t* shift, unsigned order, void* values,
+                        hipStream_t st) = 0;
+  virtual int deep_quotient(const void* mat, unsigned width, unsigned log_rows, const void* inv, const void* values,
+                            unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha, const uint64_t* scale,
+                            unsigned flags, void* out, hipStream_t st) = 0;
+  virtual int deep_info(unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
+                        unsigned* quotient_lanes_per_row) const = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -262,6 +275,7 @@ struct PlanImpl final : PlanBase {
   Shift<E, PlanImpl> shift{*this};    // the shift cache, coset transforms, low-degree extension (plan_shift.hpp)
   Matrix<E, PlanImpl> mat{*this};     // row-major matrix transforms (plan_matrix.hpp)
   Fold<E, PlanImpl> folder{*this};    // FRI fold (plan_fold.hpp)
+  Deep<E, PlanImpl> deep{*this};      // DEEP openings and quotients (plan_deep.hpp)
   Single<E, PlanImpl> single{*this};  // single-launch schedules, the in-place final pass (plan_single.hpp)
   unsigned lo_bits = 0;
   uint32_t nrand = 1, top_bits = 28;
@@ -632,6 +646,23 @@ struct PlanImpl final : PlanBase {
   int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree, uint64_t ext_w,
            const uint64_t* beta, const uint64_t* c, hipStream_t st) override {
     return folder.run(in, out, log_rows, log_arity, ext_degree, ext_w, beta, c, st);
+  }
+  int deep_points(void* inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w, const uint64_t* z,
+                  const uint64_t* c, unsigned order, hipStream_t st) override {
+    return deep.points(inv, log_rows, ext_degree, ext_w, z, c, order, st);
+  }
+  int deep_open(const void* m, unsigned width, unsigned log_rows, const void* inv, unsigned ext_degree, uint64_t ext_w,
+                const uint64_t* z, const uint64_t* c, unsigned order, void* values, hipStream_t st) override {
+    return deep.open(m, width, log_rows, inv, ext_degree, ext_w, z, c, order, values, st);
+  }
+  int deep_quotient(const void* m, unsigned width, unsigned log_rows, const void* inv, const void* values,
+                    unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha, const uint64_t* scale, unsigned fl,
+                    void* out, hipStream_t st) override {
+    return deep.quotient(m, width, log_rows, inv, values, ext_degree, ext_w, alpha, scale, fl, out, st);
+  }
+  int deep_info(unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
+                unsigned* quotient_lanes_per_row) const override {
+    return deep.info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
   }
   bool single_launch_ready() override { return single.ready(); }
 
@@ -1324,6 +1355,35 @@ int ntt_fri_fold(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_row
     plan->last = &P;
     return P.fold(d_in, d_out, log_rows, log_arity, ext_degree, ext_w, beta, shift, S(s));
   });
+}
+// DEEP openings and quotients: the plan's own engine (never the second plan)
+int ntt_deep_points(ntt_plan* plan, void* d_inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w,
+                    const uint64_t* z, const uint64_t* shift, unsigned order, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.deep_points(d_inv, log_rows, ext_degree, ext_w, z, shift, order, S(s));
+  });
+}
+int ntt_matrix_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_inv,
+                    unsigned ext_degree, uint64_t ext_w, const uint64_t* z, const uint64_t* shift, unsigned order,
+                    void* d_values, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.deep_open(d_mat, width, log_rows, d_inv, ext_degree, ext_w, z, shift, order, d_values, S(s));
+  });
+}
+int ntt_deep_quotient(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_inv,
+                      const void* d_values, unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha,
+                      const uint64_t* scale, unsigned flags, void* d_out, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.deep_quotient(d_mat, width, log_rows, d_inv, d_values, ext_degree, ext_w, alpha, scale, flags, d_out, S(s));
+  });
+}
+int ntt_deep_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
+                  unsigned* quotient_lanes_per_row) {
+  if (!plan || !plan->impl) return NTT_ERR_ARG;
+  return plan->impl->deep_info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
 }
 int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;

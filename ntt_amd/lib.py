@@ -37,6 +37,7 @@ NTT_PLAN_IMPROVED_V4 = 4096
 NTT_PLAN_ELEM32 = 8192
 NTT_MATRIX_BITREV_OUT = 1
 NTT_MATRIX_BITREV_IN = 2
+NTT_DEEP_ACCUMULATE = 1
 
 # Every symbol declared in include/ntt.h with its ctypes prototype: (restype, argtypes).
 _vp = C.c_void_p
@@ -61,6 +62,13 @@ PROTOTYPES = {
     "ntt_lde_matrix_ex": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.POINTER(C.c_uint64), C.c_uint, C.c_uint, _vp]),
     "ntt_fri_fold": (C.c_int, [_vp, _vp, _vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.POINTER(C.c_uint64),
                                C.POINTER(C.c_uint64), _vp]),
+    "ntt_deep_points": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, C.c_uint64, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64), C.c_uint, _vp]),
+    "ntt_matrix_open": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, _vp, C.c_uint, C.c_uint64, C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint64), C.c_uint, _vp, _vp]),
+    "ntt_deep_quotient": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint, _vp, _vp]),
+    "ntt_deep_info": (C.c_int, [_vp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "ntt_polymul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ntt_fill": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _vp]),
     "ntt_plan_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_uint),

@@ -420,6 +420,145 @@ class NTTPlan:
                                         _stream_ptr(stream, out.device)), "ntt_fri_fold")
         return out
 
+    # -------------------------------------------------------------------------------- DEEP openings and quotients
+    def _check_deep(self, ext_degree, ext_w, shift, log_rows, words) -> int:
+        """The scalar arguments the DEEP calls share; ``words`` = ((name, value, may_be_none), ..): sequences of
+        ``ext_degree`` canonical ints.  Returns log_rows."""
+        def is_int(v):
+            return isinstance(v, int) and not isinstance(v, bool)
+        if log_rows is None:
+            log_rows = self.log_n
+        if not is_int(log_rows) or not 0 <= log_rows <= self.log_n:
+            raise ValueError(f"log_rows must be an integer in [0, {self.log_n}], not {log_rows!r}")
+        if not is_int(ext_degree) or ext_degree not in (1, 2, 4):
+            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
+        if ext_degree > 1 and (not is_int(ext_w) or not 0 < ext_w < self.p):
+            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
+        for name, value, optional in words:
+            if value is None and optional:
+                continue
+            try:
+                vals = list(value)
+            except TypeError:
+                raise ValueError(f"{name} must be a sequence of {ext_degree} integers, not {value!r}") from None
+            if isinstance(value, str) or len(vals) != ext_degree or not all(is_int(v) and 0 <= v < self.p for v in vals):
+                raise ValueError(f"{name} must be {ext_degree} canonical integers (0 <= {name}[j] < p), not {value!r}")
+        self._check_matrix_ex(shift, True, "")
+        return log_rows
+
+    def _check_on_domain(self, z, shift, log_rows) -> None:
+        if not any(z[1:]) and pow(z[0], 1 << log_rows, self.p) == pow(1 if shift is None else shift, 1 << log_rows, self.p):
+            raise ValueError("z lies on the evaluation domain shift*<w_N>")
+
+    @staticmethod
+    def _check_no_overlap(out, out_name, out_bytes, inputs) -> None:
+        b0 = out.data_ptr()
+        for t, name, nbytes in inputs:
+            a0 = t.data_ptr()
+            if a0 < b0 + out_bytes and b0 < a0 + nbytes:
+                raise ValueError(f"{name} and {out_name} overlap")
+
+    def deep_points(self, out: torch.Tensor, z: Sequence[int], *, ext_degree: int = 1, ext_w: int = 0,
+                    shift: Optional[int] = None, bitrev: bool = False, log_rows: Optional[int] = None,
+                    stream=None) -> torch.Tensor:
+        """``out`` = [N = 2^log_rows][ext_degree] receives (z - x_i)^-1, x_i = shift w_N^i (``bitrev``:
+        w_N^bitrev(i), the row order of ``lde_matrix(..., bitrev_out=True)``), in the working form of
+        ntt_deep_points: times 2^32 mod p on 4-byte elements, the plain value on Goldilocks.  ``z`` is
+        ``ext_degree`` canonical ints and must not lie on the domain."""
+        log_rows = self._check_deep(ext_degree, ext_w, shift, log_rows, (("z", z, False),))
+        if not isinstance(bitrev, bool):
+            raise ValueError(f"bitrev must be a bool, not {bitrev!r}")
+        z = list(z)
+        self._check_on_domain(z, shift, log_rows)
+        self._check_matrix(out, 1 << log_rows, ext_degree, "out")
+        self._check_matrix_device(out, "out")
+        sh = None if shift is None else _u64_array([shift])
+        _L.check(self._lib.ntt_deep_points(self._h, C.c_void_p(out.data_ptr()), int(log_rows), int(ext_degree),
+                                           int(ext_w) if ext_degree > 1 else 0, _u64_array(z), sh,
+                                           _L.NTT_MATRIX_BITREV_OUT if bitrev else 0,
+                                           _stream_ptr(stream, out.device)), "ntt_deep_points")
+        return out
+
+    def open_matrix(self, mat: torch.Tensor, width: int, inv: torch.Tensor, values: torch.Tensor, z: Sequence[int], *,
+                    ext_degree: int = 1, ext_w: int = 0, shift: Optional[int] = None, bitrev: bool = False,
+                    log_rows: Optional[int] = None, stream=None) -> torch.Tensor:
+        """``values`` = [width][ext_degree] receives p_j(z) for every column j of ``mat`` = [N][width], the
+        evaluations of p_j (degree < N) on shift*<w_N> (ntt_matrix_open); ``inv`` is ``deep_points``' output for
+        the same z, shift, bitrev, log_rows and extension."""
+        log_rows = self._check_deep(ext_degree, ext_w, shift, log_rows, (("z", z, False),))
+        if not isinstance(bitrev, bool):
+            raise ValueError(f"bitrev must be a bool, not {bitrev!r}")
+        z = list(z)
+        self._check_on_domain(z, shift, log_rows)
+        rows = 1 << log_rows
+        self._check_deep_matrix(mat, rows, width)
+        self._check_matrix(inv, rows, ext_degree, "inv")
+        self._check_matrix(values, width, ext_degree, "values")
+        eb = self.elem_bytes
+        self._check_no_overlap(values, "values", width * ext_degree * eb,
+                               ((mat, "mat", rows * width * eb), (inv, "inv", rows * ext_degree * eb)))
+        for t, what in ((mat, "mat"), (inv, "inv"), (values, "values")):
+            self._check_matrix_device(t, what)
+        sh = None if shift is None else _u64_array([shift])
+        _L.check(self._lib.ntt_matrix_open(self._h, C.c_void_p(mat.data_ptr()), int(width), int(log_rows),
+                                           C.c_void_p(inv.data_ptr()), int(ext_degree),
+                                           int(ext_w) if ext_degree > 1 else 0, _u64_array(z), sh,
+                                           _L.NTT_MATRIX_BITREV_OUT if bitrev else 0, C.c_void_p(values.data_ptr()),
+                                           _stream_ptr(stream, values.device)), "ntt_matrix_open")
+        return values
+
+    def _check_deep_matrix(self, mat: torch.Tensor, rows: int, width) -> None:
+        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if rows * width >= 1 << 32:
+            raise ValueError(f"2^log_rows * width must stay below 2^32, not {rows} * {width}")
+        if not mat.is_contiguous() or mat.dtype != self.dtype:
+            raise ValueError(f"mat must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the plan's "
+                             "element layout")
+        if mat.numel() * mat.element_size() != rows * width * self.elem_bytes:
+            raise ValueError(f"mat: expected {rows} rows of {width} elements of {self.elem_bytes} bytes")
+
+    def deep_quotient(self, mat: torch.Tensor, width: int, inv: torch.Tensor, values: torch.Tensor, out: torch.Tensor,
+                      alpha: Sequence[int], *, scale: Optional[Sequence[int]] = None, accumulate: bool = False,
+                      ext_degree: int = 1, ext_w: int = 0, log_rows: Optional[int] = None, stream=None) -> torch.Tensor:
+        """``out`` = [N][ext_degree] receives scale * inv[i] * (sum_j alpha^j values[j] - sum_j alpha^j mat[i][j])
+        = scale * sum_j alpha^j (p_j(x_i) - p_j(z)) / (x_i - z) (ntt_deep_quotient), in ``inv``'s row order;
+        ``accumulate`` adds into ``out``.  ``alpha`` and ``scale`` (None: 1) are ``ext_degree`` canonical ints."""
+        log_rows = self._check_deep(ext_degree, ext_w, None, log_rows, (("alpha", alpha, False), ("scale", scale, True)))
+        if not isinstance(accumulate, bool):
+            raise ValueError(f"accumulate must be a bool, not {accumulate!r}")
+        rows = 1 << log_rows
+        self._check_deep_matrix(mat, rows, width)
+        self._check_matrix(inv, rows, ext_degree, "inv")
+        self._check_matrix(values, width, ext_degree, "values")
+        self._check_matrix(out, rows, ext_degree, "out")
+        eb = self.elem_bytes
+        self._check_no_overlap(out, "out", rows * ext_degree * eb,
+                               ((mat, "mat", rows * width * eb), (inv, "inv", rows * ext_degree * eb),
+                                (values, "values", width * ext_degree * eb)))
+        for t, what in ((mat, "mat"), (inv, "inv"), (values, "values"), (out, "out")):
+            self._check_matrix_device(t, what)
+        _L.check(self._lib.ntt_deep_quotient(self._h, C.c_void_p(mat.data_ptr()), int(width), int(log_rows),
+                                             C.c_void_p(inv.data_ptr()), C.c_void_p(values.data_ptr()), int(ext_degree),
+                                             int(ext_w) if ext_degree > 1 else 0, _u64_array(list(alpha)),
+                                             None if scale is None else _u64_array(list(scale)),
+                                             _L.NTT_DEEP_ACCUMULATE if accumulate else 0, C.c_void_p(out.data_ptr()),
+                                             _stream_ptr(stream, out.device)), "ntt_deep_quotient")
+        return out
+
+    def deep_info(self, width: int, *, log_rows: Optional[int] = None, ext_degree: int = 1):
+        """(open_row_chunks, quotient_lanes_per_row) of ``open_matrix`` and ``deep_quotient`` at this shape
+        (ntt_deep_info)."""
+        log_rows = self._check_deep(ext_degree, 1, None, log_rows, ())
+        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if (width << log_rows) >= 1 << 32:
+            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+        chunks, lanes = C.c_uint(), C.c_uint()
+        _L.check(self._lib.ntt_deep_info(self._h, int(width), int(log_rows), int(ext_degree), C.byref(chunks),
+                                         C.byref(lanes)), "ntt_deep_info")
+        return chunks.value, lanes.value
+
     def matrix_passes(self, width: int) -> List[int]:
         """log2 radices of the passes the matrix calls run at this width (ntt_plan_matrix_info); [] for
         sizes up to 4 rows, which one simple kernel transforms."""
