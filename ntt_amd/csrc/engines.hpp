@@ -151,6 +151,10 @@ struct Eng29 {
   // no LDS twiddle staging: a radix-256 table of Shoup pairs (20 KiB) beside the 36-KiB tile would
   // halve the workgroups per CU
   static constexpr bool LDS_TW = false;
+  // mul_u multiplies by a twiddle held in SGPRs (mulc29_a9u), so a sub-stage whose twiddle is the same
+  // in every lane of a wave reads its table entries with scalar loads (tload_u); the 384-bit class's
+  // mulc29_blk has no such form and keeps the per-lane loads
+  static constexpr bool SGPR_TW = (L == 9);
   // quotient-estimate reduction needs p's top limb >= 2^18: possible only when 29L - 18 <= 255
   static constexpr bool FASTRED = 29 * L - 18 <= 255;
   struct Tw {
@@ -225,8 +229,9 @@ struct Eng29 {
   // c < 2^6.2; x_i + c < 2^32 for the input limbs (< 2^31.6).  Per limb one 32-bit add, one MAD
   // (q pbar_i + (x_i + c)), a mask and one v_alignbit (the carry) -- instead of a 64-bit shift and a
   // 64-bit add of the zero-extended limb, whose register pairs cost the compiler extra moves.
-  // R32 = false: the 64-bit-carry form, which needs fewer registers (the column passes run at the
-  // 128-VGPR cap, where the 32-bit form spills and measured 3.6 % slower in pass 1).
+  // R32 = false: the 64-bit-carry form.  The radix-256 column passes took it while the 32-bit form
+  // spilled there (3.6 % slower in pass 1); since their wave-uniform sub-stage holds its twiddles in
+  // SGPRs the 32-bit form fits without scratch, and every pass takes it (NTT_COL_R32_BELOW).
   template <bool R32 = true>
   __device__ static __forceinline__ void reduce_top(uint32_t (&x)[W], const Args& A) {
     const float qf = __builtin_fmaf((float)x[L - 1], A.red_inv, -0x1p-15f);
@@ -306,6 +311,27 @@ struct Eng29 {
 #pragma unroll
     for (int q = 0; q < TW / 4; ++q) {
       const uint4 v = p[q];
+      const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = 4 * q + r;
+        if (i < L) t.w[i] = vv[r];
+        else if (i < 2 * L) t.ws[i - L] = vv[r];
+      }
+    }
+  }
+  // The entry at an index that is the same in every lane of the wave (formed from a
+  // __builtin_amdgcn_readfirstlane value): read through the constant address space, so that the words
+  // arrive by scalar loads into SGPRs, where mul_u takes them -- no vector-memory instruction and no
+  // VGPR for the pair.  Only for tables that no store of this launch touches (the scalar cache is not
+  // coherent with them): the plans' twiddle tables, written by an earlier launch.
+  __device__ static __forceinline__ void tload_u(Tw& t, const uint32_t* __restrict__ tab, uint32_t idx) {
+    typedef uint32_t V4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(4))) V4* CP;
+    const CP p = (CP)(tab + (size_t)idx * TW);
+#pragma unroll
+    for (int q = 0; q < TW / 4; ++q) {
+      const V4 v = p[q];
       const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -435,6 +461,7 @@ struct Eng32 {
   // Shoup pairs) is staged into LDS while the tile's HBM loads are in flight; sub-stages read their
   // twiddles from LDS instead of issuing L1/L2 loads beside the data stream
   static constexpr bool LDS_TW = NTT_P_LDS_TW;
+  static constexpr bool SGPR_TW = false;  // no SGPR-twiddle product
   static constexpr int WAVES_PER_EU = 4;
   static constexpr bool FASTRED = false;
   struct Tw {
@@ -559,6 +586,7 @@ struct Eng64G {
   static constexpr bool NARROW_FIRST = true;  // HBM-bound like the P path: pass 1 reads wider runs
   static constexpr bool SHOUP_OUTER = false;
   static constexpr bool LDS_TW = false;
+  static constexpr bool SGPR_TW = false;
   static constexpr int WAVES_PER_EU = 4;
   static constexpr bool FASTRED = false;
   struct Tw {
@@ -676,6 +704,7 @@ struct Eng31 {
   static constexpr bool NARROW_FIRST = true;
   static constexpr bool SHOUP_OUTER = false;
   static constexpr bool LDS_TW = true;
+  static constexpr bool SGPR_TW = false;
   static constexpr int WAVES_PER_EU = 4;
   static constexpr bool FASTRED = false;
   struct Tw {

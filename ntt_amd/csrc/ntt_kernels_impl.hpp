@@ -287,9 +287,19 @@ __device__ __forceinline__ void substage(uint32_t (&x)[E::EPT][E::W], uint32_t (
         });
       };
       if constexpr (Uniform<LOGR, ept_log<E>(), NT, s>::on) {
-        if (__builtin_amdgcn_readfirstlane(cp) == 0) {  // wave-uniform: w^0 = 1, only bring the bounds down
+        const uint32_t cps = __builtin_amdgcn_readfirstlane(cp);  // the wave's class, in an SGPR
+        if (cps == 0) {  // wave-uniform: w^0 = 1, only bring the bounds down
           static_for<Q - 1>([&](auto K1) {
             E::template reduce<E::IN * Q, E::IN, FAST, R32>(x[j * Q + brev_bits(K1 + 1, qb)], A.F);
+          });
+        } else if constexpr (E::SGPR_TW && !LTW) {
+          // one table entry per wave: scalar address, scalar loads, the pair stays in SGPRs.  One
+          // entry at a time: three at once are 54 SGPRs beside pbar, pc and the w_8 words.
+          static_for<Q - 1>([&](auto K1) {
+            constexpr int k = K1 + 1;
+            typename E::Tw w;
+            E::tload_u(w, A.tw_int, (cps * k) << (LOGR - lN));
+            E::mul_u(x[j * Q + brev_bits(k, qb)], w, A.F);
           });
         } else {
           twiddles();
@@ -319,11 +329,14 @@ enum : int { PRO_NONE = 0, PRO_PW = 1, PRO_COSET = 2, PRO_LDE = 3 };
 // FSM: four-step addressing (PassArgs::fs) compiled in: 0 = plain batched transforms (every
 // product path), 1 = chunk maps / interleave, 2 = the same plus the output twiddle epilogue.
 // SHTW: the column pass's full outer-twiddle table holds Shoup pairs (PassArgs::tw_sh).
-// Column passes of radix < 2^NTT_COL_R32_BELOW also take the 32-bit-carry reduce_top: below radix
-// 256 they fit 122-123 VGPRs with it and no spills (radix 256 spills 28 B), -1.0 % on 2^28's four
-// radix-128 passes (profiles/r02_uni/col_r32_ab_*.txt).
+// Column passes of radix < 2^NTT_COL_R32_BELOW also take the 32-bit-carry reduce_top: -1.0 % on 2^28's
+// four radix-128 passes (profiles/r02_uni/col_r32_ab_*.txt).  Radix 256 used to spill with it (28 B, 3.6 %
+// slower in pass 1) and stayed on the 64-bit-carry form until the wave-uniform sub-stage took its
+// twiddles in SGPRs: with 18 VGPRs fewer live there, every radix-256 column pass compiles to 119-123
+// VGPRs and no scratch (16-40 B with the 64-bit form), -1.3 % at 2^24 (profiles/r07_sgpr_tw/).  So 9: all
+// the tile's column radices; 8 rebuilds the former split.
 #ifndef NTT_COL_R32_BELOW
-#define NTT_COL_R32_BELOW 8
+#define NTT_COL_R32_BELOW 9
 #endif
 // ---- in-place final pass with the digit reversal fused (NTT_PLAN_IN_PLACE; k_final_ipn, ntt_inplace_impl.hpp).
 // The final pass's outputs of slab `mid` belong in slab `midrev` (the palindromic schedule makes the
