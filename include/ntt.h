@@ -410,6 +410,64 @@ int ntt_deep_quotient(ntt_plan* plan, const void* d_mat, unsigned width, unsigne
 int ntt_deep_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned ext_degree,
                   unsigned* open_row_chunks, unsigned* quotient_lanes_per_row);
 
+/* Poseidon2 Merkle commitments and openings of a row-major matrix: the step between ntt_lde_matrix_ex,
+ * ntt_deep_quotient, ntt_fri_fold and the next of them.  Every row of M = d_mat = [N = 2^log_rows][width] is one leaf.
+ * With t the permutation's width and D = t / 2 (the sponge's rate and the digest length, in base-field elements):
+ * t = 16 on plans of 4-byte elements (NTT_FIELD_BABYBEAR, NTT_FIELD_KOALABEAR, NTT_PLAN_ELEM32), t = 8 on
+ * NTT_FIELD_GOLDILOCKS: the shapes PaddingFreeSponge<Perm, t, D, D> and TruncatedPermutation<Perm, 2, D, t>.
+ * The parameters are the caller's; the library ships no round constants and claims bit-compatibility with no
+ * particular prover: that is a matter of the constants supplied.
+ *   The permutation: M_E; rounds_f / 2 external rounds; rounds_p internal rounds; rounds_f / 2 external rounds.
+ *     External round r: s_i += ext_rc[r][i]; s_i = s_i^a; s = M_E s.  M_E: M4 = [[2,3,1,1],[1,2,3,1],[1,1,2,3],
+ *     [3,1,1,2]] on each group of four adjacent elements, then to every element the sum of the elements at the same
+ *     position mod 4 over all groups (circ(2 M4, M4, .., M4)).  Internal round r: s_0 += int_rc[r]; s_0 = s_0^a;
+ *     sigma = sum_i s_i; s_i = int_diag[i] s_i + sigma.
+ *   The leaf hash of a row x_0..x_{width-1}: s = 0^t; for each chunk of up to D consecutive elements, overwrite
+ *     s_0..s_{len-1} with it (the other positions stay as they are, for a short last chunk too) and permute; the
+ *     digest is s_0..s_{D-1}.  Compression: s = left || right, permute, the digest is s_0..s_{D-1}.
+ *   The tree: layer 0 is the N leaf digests in the order the rows are stored (a bit-reversed matrix gives a
+ *     bit-reversed tree); node i of layer l is the compression of nodes 2i and 2i + 1 of layer l - 1.  d_tree is
+ *     [2N - 1][D] elements, layer l starting at node 2N - 2^(L-l+1), L = log_rows; the root is node 2N - 2.  A cap
+ *     is a layer of d_tree.
+ * The matrix, the states and the digests are in the plan's I/O form: on NTT_PLAN_MONTGOMERY_IO plans they are the
+ * Montgomery form of the same field elements (digest_mont = digest_canon 2^32 mod p).  The parameters are always
+ * canonical host words.
+ *   ntt_plan_set_poseidon2  width = t; sbox_degree a in {3, 5, 7} with gcd(a, p - 1) = 1; rounds_f even, 2..16;
+ *     rounds_p 0..64 (int_rc may be NULL at 0); ext_rc [rounds_f][t], int_rc [rounds_p], int_diag [t].  Blocking,
+ *     like plan creation; it must not race calls in flight on the plan; it may be called again to replace the
+ *     parameters.  The plan keeps them in a device buffer of its own, allocated at the first call, its size
+ *     independent of N.
+ *   ntt_poseidon2_permute  d_states [count][t], permuted in place: the primitive, for transcripts and the caller's
+ *     own sponges.  One launch.
+ *   ntt_merkle_commit  d_tree from d_mat, which it leaves unmodified: one leaf launch (a lane a row, the rows of a
+ *     workgroup through LDS, every element read once), one launch per layer (a lane a parent) down to 2^tail_log
+ *     nodes, then one workgroup for the last tail_log layers through LDS.
+ *   ntt_merkle_open  for query q with i = d_index[q] & (N - 1) (the indices live on the device; an index >= N
+ *     wraps and nothing faults): d_rows[q] = row i of d_mat, and d_paths[q][l] = node (i >> l) ^ 1 of layer l, the
+ *     sibling, l < log_rows.  d_mat and d_rows may both be NULL to skip the rows; d_paths may be NULL at
+ *     log_rows 0, where a path is empty.  One launch.
+ *   ntt_merkle_info  D, the elements of d_tree, the launches of ntt_merkle_commit and tail_log at (width,
+ *     log_rows).  No launch; it needs no parameters.
+ * A FRI layer: a fold output [M][d] in bit-reversed order, taken as [M >> k][d << k], has each fibre of the next
+ * fold of arity 2^k as one row, so its commitment is ntt_merkle_commit with width = d << k and log_rows less k.
+ * The three launching calls are asynchronous on hip_stream and never synchronise the host.  Any element-aligned
+ * pointer is accepted; 16-byte accesses are used where the pointers (and the rows) are 16-byte aligned.
+ * Engines: as the matrix calls; plans of fields 0-2 and of custom 4- and 6-limb moduli return NTT_ERR_ARG.
+ * NTT_ERR_ARG before any launch, the buffers untouched: a null plan or pointer (but for the cases above), width 0,
+ * N width >= 2^32, log_rows above the plan's log_n, nq 0, count 0, exactly one of d_mat and d_rows NULL, overlapping
+ * byte ranges of an output with an input, NTT_PLAN_TWIDDLE_ONLY plans, a launching call before the parameters are
+ * set; from ntt_plan_set_poseidon2: a width other than the engine's t, a degree outside {3, 5, 7} or sharing a
+ * factor with p - 1, rounds_f odd or outside 2..16, rounds_p above 64, a parameter word >= p. */
+int ntt_plan_set_poseidon2(ntt_plan* plan, unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p,
+                           const uint64_t* ext_rc, const uint64_t* int_rc, const uint64_t* int_diag);
+int ntt_poseidon2_permute(ntt_plan* plan, void* d_states, uint64_t count, void* hip_stream);
+int ntt_merkle_commit(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, void* d_tree,
+                      void* hip_stream);
+int ntt_merkle_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_tree,
+                    const uint32_t* d_index, unsigned nq, void* d_rows, void* d_paths, void* hip_stream);
+int ntt_merkle_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned* digest_elems,
+                    uint64_t* tree_elems, unsigned* launches, unsigned* tail_log);
+
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */
 int ntt_pointwise_mul(ntt_plan* plan, const void* d_a, const void* d_b, void* d_c, void* hip_stream);
@@ -471,7 +529,8 @@ int ntt_plan_last_launch_ms(ntt_plan* plan, float* ms, unsigned max_launches, un
  * transform per workgroup; r several per workgroup; i in-place final pass with the digit reversal;
  * d digit-reversal swap; b single launch; n naive; x FRI fold, with log_arity for the radix; z DEEP points;
  * o open: strip sums, e open: the chunks and the scalars; a quotient: the alpha table, q quotient: the rows), ""
- * when unlabelled.  NTT_ERR_ARG when `cap`
+ * when unlabelled.  The Merkle calls: h leaf hash; m tree layers, with the number of layers the launch covers for
+ * the radix; g open (gather); p permute.  NTT_ERR_ARG when `cap`
  * bytes do not hold them.  New (round 6): benchmarks pair per-launch PMC bytes with launches by
  * label, not by position. */
 int ntt_plan_last_launch_labels(ntt_plan* plan, char* buf, unsigned cap);

@@ -46,6 +46,7 @@ SOURCES += [f"ntt_e31_{k}.hip" for k in ("col", "single", "fin", "misc", "rows")
 SOURCES += ["ntt_eg_mat.hip", "ntt_e31_mat.hip"]  # row-major matrix passes, the strip form (ntt_*_matrix)
 SOURCES += ["ntt_eg_fold.hip", "ntt_e31_fold.hip"]  # FRI fold of bit-reversed coset evaluations (ntt_fri_fold)
 SOURCES += ["ntt_eg_deep.hip", "ntt_e31_deep.hip"]  # DEEP openings and quotients of evaluation matrices (ntt_deep_*, ntt_matrix_open)
+SOURCES += ["ntt_eg_hash.hip", "ntt_e31_hash.hip"]  # Poseidon2 Merkle commitments and openings (ntt_poseidon2_permute, ntt_merkle_*)
 SOURCES += ["ntt_plan.cpp", "ntt_rplan.cpp", "ntt_multi.cpp"]
 ARCH = os.environ.get("NTT_OFFLOAD_ARCH", "gfx950")
 

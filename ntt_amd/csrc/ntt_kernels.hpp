@@ -6,6 +6,7 @@
 #include "engines.hpp"
 #include "fieldext.hpp"
 #include "plan_fused.hpp"
+#include "poseidon2.hpp"
 
 namespace ntt {
 
@@ -458,6 +459,63 @@ hipError_t launch_deep_qpro(unsigned d, const uint32_t* values, uint32_t* scr, c
 template <class E>
 hipError_t launch_deep_quotient(unsigned d, const uint32_t* mat, const uint32_t* inv, const uint32_t* scr, uint32_t* out,
                                 const DeepArgs<E>& A, hipStream_t st);
+
+// ---- Poseidon2 Merkle commitments and openings of a row-major matrix (ntt_poseidon2_permute, ntt_merkle_commit,
+// ntt_merkle_open; kernels in ntt_hash_impl.hpp, instances in ntt_eg_hash.hip and ntt_e31_hash.hip: the HasMat
+// engines).  The permutation and its constant table: poseidon2.hpp.
+template <class E>
+using hash_k_t = std::conditional_t<std::is_same_v<E, Eng31>, p2::P31, p2::P64>;
+// The shape decisions, shared by the launchers, the kernels and ntt_merkle_info.  memw = E::MEMW.
+struct MerkleShape {
+  static constexpr unsigned BT = 256;       // threads of a leaf, layer, tail or permute workgroup: a row, parent or state each
+  static constexpr unsigned TAIL_LOG = 9;   // the tail workgroup takes a layer of 2^9 nodes: BT parents in its first step
+  static constexpr unsigned OPEN_BT = 64;   // open: one wave per query
+  __host__ __device__ static constexpr unsigned width_t(int memw) { return memw == 1 ? 16u : 8u; }  // the permutation's width
+  // leaf: columns of a row tile in LDS (128 B of a row: four absorptions), rows at a pitch of one element more
+  __host__ __device__ static constexpr unsigned chunk_cols(int memw) { return memw == 1 ? 32u : 16u; }
+  __host__ __device__ static constexpr unsigned tail_log(unsigned log_rows) { return log_rows < TAIL_LOG ? log_rows : TAIL_LOG; }
+  // the leaf launch, one per layer above the tail, the tail
+  __host__ __device__ static constexpr unsigned launches(unsigned log_rows) {
+    return 1 + (log_rows - tail_log(log_rows)) + (log_rows ? 1u : 0u);
+  }
+  // first node of layer l of a tree over 2^log_rows leaves
+  __host__ __device__ static constexpr uint64_t layer_start(unsigned log_rows, unsigned l) {
+    return (2ull << log_rows) - ((2ull << log_rows) >> l);
+  }
+};
+template <class E>
+struct HashArgs {
+  hash_k_t<E> K;   // the field's constants and the I/O form
+  uint32_t* dbg;   // checked build: the plan's status word
+  uint32_t rounds_f, rounds_p;
+  uint32_t log_rows, width;
+  uint32_t vec;       // permute: the states, leaf: the matrix is 16-byte aligned and a row is whole 16-byte words: vector access
+  uint32_t vec_tree;  // the tree is 16-byte aligned
+  uint32_t layers; // tail: the layers it runs
+  uint32_t nq;
+  uint64_t count;  // permute: states; layer: parents
+  uint64_t in_node, out_node;  // layer and tail: first node of the children's layer and of the parents'
+  size_t mat_elems, tree_elems, st_elems, idx_elems, rows_elems, paths_elems;  // checked build: elements of each buffer
+};
+// sbox_degree 3, 5 or 7 in each; tab: the plan's constant table (poseidon2.hpp Layout).
+// permute: states [count][T] in place.  leaf: mat [N][width] -> layer 0 of tree.  layer: count parents at out_node
+// from the children at in_node.  tail: `layers` layers from the 2^layers nodes at in_node, one workgroup.
+// open: rows (null: none) and paths of nq queries.
+template <class E>
+hipError_t launch_p2_permute(unsigned sbox_degree, uint32_t* states, const deep_val_t<E>* tab, const HashArgs<E>& A,
+                             hipStream_t st);
+template <class E>
+hipError_t launch_merkle_leaf(unsigned sbox_degree, const uint32_t* mat, uint32_t* tree, const deep_val_t<E>* tab,
+                              const HashArgs<E>& A, hipStream_t st);
+template <class E>
+hipError_t launch_merkle_layer(unsigned sbox_degree, uint32_t* tree, const deep_val_t<E>* tab, const HashArgs<E>& A,
+                               hipStream_t st);
+template <class E>
+hipError_t launch_merkle_tail(unsigned sbox_degree, uint32_t* tree, const deep_val_t<E>* tab, const HashArgs<E>& A,
+                              hipStream_t st);
+template <class E>
+hipError_t launch_merkle_open(const uint32_t* mat, const uint32_t* tree, const uint32_t* index, uint32_t* rows,
+                              uint32_t* paths, const HashArgs<E>& A, hipStream_t st);
 
 template <class E>
 hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,

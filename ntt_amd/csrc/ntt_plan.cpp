@@ -90,6 +90,7 @@ struct FirstPass {
 // the plan's features, each a struct the plan owns and hands a reference to itself; they name FirstPass
 #include "plan_deep.hpp"    // Deep<E, Plan>: DEEP openings and quotients of evaluation matrices
 #include "plan_fold.hpp"    // Fold<E, Plan>: ntt_fri_fold
+#include "plan_hash.hpp"    // Hash<E, Plan>: Poseidon2 Merkle commitments and openings
 #include "plan_matrix.hpp"  // Matrix<E, Plan>: the row-major matrix transforms
 #include "plan_rivals.hpp"  // Rivals<E, Plan>: the rival schedules
 #include "plan_shift.hpp"   // Shift<E, Plan>: the shift cache, coset transforms, low-degree extension
@@ -153,6 +154,16 @@ struct PlanBase {
                             unsigned flags, void* out, hipStream_t st) = 0;
   virtual int deep_info(unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
                         unsigned* quotient_lanes_per_row) const = 0;
+  // Poseidon2 Merkle commitments and openings of a row-major matrix (ntt_plan_set_poseidon2, ntt_poseidon2_permute,
+  // ntt_merkle_commit, ntt_merkle_open, ntt_merkle_info)
+  virtual int poseidon2_set(unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p,
+                            const uint64_t* ext_rc, const uint64_t* int_rc, const uint64_t* int_diag) = 0;
+  virtual int poseidon2_permute(void* states, uint64_t count, hipStream_t st) = 0;
+  virtual int merkle_commit(const void* mat, unsigned width, unsigned log_rows, void* tree, hipStream_t st) = 0;
+  virtual int merkle_open(const void* mat, unsigned width, unsigned log_rows, const void* tree, const uint32_t* index,
+                          unsigned nq, void* rows, void* paths, hipStream_t st) = 0;
+  virtual int merkle_info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems,
+                          unsigned* launches, unsigned* tail_log) const = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -276,6 +287,7 @@ struct PlanImpl final : PlanBase {
   Matrix<E, PlanImpl> mat{*this};     // row-major matrix transforms (plan_matrix.hpp)
   Fold<E, PlanImpl> folder{*this};    // FRI fold (plan_fold.hpp)
   Deep<E, PlanImpl> deep{*this};      // DEEP openings and quotients (plan_deep.hpp)
+  Hash<E, PlanImpl> hash{*this};      // Poseidon2 Merkle commitments and openings (plan_hash.hpp)
   Single<E, PlanImpl> single{*this};  // single-launch schedules, the in-place final pass (plan_single.hpp)
   unsigned lo_bits = 0;
   uint32_t nrand = 1, top_bits = 28;
@@ -663,6 +675,22 @@ struct PlanImpl final : PlanBase {
   int deep_info(unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
                 unsigned* quotient_lanes_per_row) const override {
     return deep.info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
+  }
+  int poseidon2_set(unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p, const uint64_t* ext_rc,
+                    const uint64_t* int_rc, const uint64_t* int_diag) override {
+    return hash.set(width, sbox_degree, rounds_f, rounds_p, ext_rc, int_rc, int_diag);
+  }
+  int poseidon2_permute(void* states, uint64_t count, hipStream_t st) override { return hash.permute(states, count, st); }
+  int merkle_commit(const void* m, unsigned width, unsigned log_rows, void* tree, hipStream_t st) override {
+    return hash.commit(m, width, log_rows, tree, st);
+  }
+  int merkle_open(const void* m, unsigned width, unsigned log_rows, const void* tree, const uint32_t* index, unsigned nq,
+                  void* rows, void* paths, hipStream_t st) override {
+    return hash.open(m, width, log_rows, tree, index, nq, rows, paths, st);
+  }
+  int merkle_info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems, unsigned* launches,
+                  unsigned* tail_log) const override {
+    return hash.info(width, log_rows, digest_elems, tree_elems, launches, tail_log);
   }
   bool single_launch_ready() override { return single.ready(); }
 
@@ -1384,6 +1412,37 @@ int ntt_deep_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsig
                   unsigned* quotient_lanes_per_row) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;
   return plan->impl->deep_info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
+}
+// Poseidon2 Merkle commitments and openings: the plan's own engine (never the second plan)
+int ntt_plan_set_poseidon2(ntt_plan* plan, unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p,
+                           const uint64_t* ext_rc, const uint64_t* int_rc, const uint64_t* int_diag) {
+  return on_device(plan, [&](PlanBase& P) {
+    return P.poseidon2_set(width, sbox_degree, rounds_f, rounds_p, ext_rc, int_rc, int_diag);
+  });
+}
+int ntt_poseidon2_permute(ntt_plan* plan, void* d_states, uint64_t count, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.poseidon2_permute(d_states, count, S(s));
+  });
+}
+int ntt_merkle_commit(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, void* d_tree, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.merkle_commit(d_mat, width, log_rows, d_tree, S(s));
+  });
+}
+int ntt_merkle_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_tree,
+                    const uint32_t* d_index, unsigned nq, void* d_rows, void* d_paths, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.merkle_open(d_mat, width, log_rows, d_tree, d_index, nq, d_rows, d_paths, S(s));
+  });
+}
+int ntt_merkle_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems,
+                    unsigned* launches, unsigned* tail_log) {
+  if (!plan || !plan->impl) return NTT_ERR_ARG;
+  return plan->impl->merkle_info(width, log_rows, digest_elems, tree_elems, launches, tail_log);
 }
 int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;

@@ -22,6 +22,11 @@ FIELDS = {
 # NTTPlan.fri_fold takes them as ext_degree and ext_w.
 EXTENSIONS = {3: (2, 7), 4: (4, 11), 5: (4, 3)}
 
+# The usual Poseidon2 shapes of those fields, field id -> (t, S-box degree, rounds_f, rounds_p): plain numbers for
+# NTTPlan.set_poseidon2, which takes the round constants and the diagonal from the caller (none are shipped; they
+# must be the verifier's).
+POSEIDON2_SHAPES = {3: (8, 7, 8, 22), 4: (16, 7, 8, 13), 5: (16, 3, 8, 20)}
+
 
 def field_params(field_id: int):
     name, p, g = FIELDS[field_id]

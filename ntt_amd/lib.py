@@ -69,6 +69,13 @@ PROTOTYPES = {
     "ntt_deep_quotient": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint, _vp, _vp]),
     "ntt_deep_info": (C.c_int, [_vp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "ntt_plan_set_poseidon2": (C.c_int, [_vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "ntt_poseidon2_permute": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "ntt_merkle_commit": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, _vp, _vp]),
+    "ntt_merkle_open": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, _vp, _vp, _vp]),
+    "ntt_merkle_info": (C.c_int, [_vp, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint64),
+                                  C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "ntt_polymul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ntt_fill": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _vp]),
     "ntt_plan_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_uint),

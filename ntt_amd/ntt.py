@@ -559,6 +559,159 @@ class NTTPlan:
                                          C.byref(lanes)), "ntt_deep_info")
         return chunks.value, lanes.value
 
+    # -------------------------------------------------------------------------------- Poseidon2 Merkle commitments
+    @property
+    def poseidon2_width(self) -> int:
+        """The permutation's width t on this plan's engine: 16 on 4-byte elements, 8 on Goldilocks (0: no hashing)."""
+        if self.elem32:
+            return 16
+        return 8 if (self.limbs64 == 1 and self.p == FIELDS[3][1]) else 0
+
+    @staticmethod
+    def _is_int(v) -> bool:
+        return isinstance(v, int) and not isinstance(v, bool)
+
+    def _check_hashing(self) -> int:
+        t = self.poseidon2_width
+        if not t:
+            raise ValueError("Poseidon2 hashing needs a Goldilocks plan or a plan of 4-byte elements")
+        return t
+
+    def set_poseidon2(self, sbox_degree: int, rounds_f: int, rounds_p: int, ext_rc, int_rc: Sequence[int],
+                      int_diag: Sequence[int], *, width: Optional[int] = None) -> None:
+        """The Poseidon2 parameters of this plan's hashing calls (ntt_plan_set_poseidon2): S-box degree 3, 5 or 7
+        coprime to p - 1, ``rounds_f`` even in [2, 16], ``rounds_p`` in [0, 64], ``ext_rc`` = rounds_f rows of t
+        canonical ints, ``int_rc`` = rounds_p, ``int_diag`` = t of them.  Blocking; may be called again."""
+        t = self._check_hashing()
+        if width is not None and (not self._is_int(width) or width != t):
+            raise ValueError(f"width must be {t} on this plan, not {width!r}")
+        if not self._is_int(sbox_degree) or sbox_degree not in (3, 5, 7):
+            raise ValueError(f"sbox_degree must be 3, 5 or 7, not {sbox_degree!r}")
+        if (self.p - 1) % sbox_degree == 0:
+            raise ValueError(f"sbox_degree {sbox_degree} divides p - 1: x^{sbox_degree} is no permutation of the field")
+        if not self._is_int(rounds_f) or not 2 <= rounds_f <= 16 or rounds_f % 2:
+            raise ValueError(f"rounds_f must be an even integer in [2, 16], not {rounds_f!r}")
+        if not self._is_int(rounds_p) or not 0 <= rounds_p <= 64:
+            raise ValueError(f"rounds_p must be an integer in [0, 64], not {rounds_p!r}")
+
+        def words(name, value, count):
+            try:
+                vals = list(value)
+            except TypeError:
+                raise ValueError(f"{name} must be a sequence of {count} integers, not {value!r}") from None
+            if isinstance(value, str) or len(vals) != count or not all(self._is_int(v) and 0 <= v < self.p for v in vals):
+                raise ValueError(f"{name} must be {count} canonical integers (0 <= v < p)")
+            return vals
+
+        try:
+            ext_rows = list(ext_rc)
+        except TypeError:
+            raise ValueError(f"ext_rc must be {rounds_f} rows of {t} integers, not {ext_rc!r}") from None
+        if isinstance(ext_rc, str) or len(ext_rows) != rounds_f:
+            raise ValueError(f"ext_rc must be {rounds_f} rows of {t} integers")
+        ext = [v for r, row in enumerate(ext_rows) for v in words(f"ext_rc[{r}]", row, t)]
+        irc = words("int_rc", int_rc, rounds_p)
+        diag = words("int_diag", int_diag, t)
+        _L.check(self._lib.ntt_plan_set_poseidon2(self._h, t, int(sbox_degree), int(rounds_f), int(rounds_p),
+                                                  _u64_array(ext), _u64_array(irc) if irc else None, _u64_array(diag)),
+                 "ntt_plan_set_poseidon2")
+        self._poseidon2 = (int(sbox_degree), int(rounds_f), int(rounds_p))
+
+    def _check_hash_call(self, width, log_rows) -> int:
+        """The arguments the Merkle calls share.  Returns log_rows."""
+        self._check_hashing()
+        if getattr(self, "_poseidon2", None) is None:
+            raise ValueError("set_poseidon2 must be called first")
+        if log_rows is None:
+            log_rows = self.log_n
+        if not self._is_int(log_rows) or not 0 <= log_rows <= self.log_n:
+            raise ValueError(f"log_rows must be an integer in [0, {self.log_n}], not {log_rows!r}")
+        if not self._is_int(width) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if (width << log_rows) >= 1 << 32:
+            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+        return log_rows
+
+    def poseidon2_permute(self, states: torch.Tensor, stream=None) -> torch.Tensor:
+        """Permute ``states`` = [count][t] in place (ntt_poseidon2_permute)."""
+        t = self._check_hashing()
+        if getattr(self, "_poseidon2", None) is None:
+            raise ValueError("set_poseidon2 must be called first")
+        if not isinstance(states, torch.Tensor) or not states.is_contiguous() or states.dtype != self.dtype:
+            raise ValueError(f"states must be a contiguous {'int32' if self.elem32 else 'int64'} tensor")
+        if states.numel() == 0 or states.numel() % t:
+            raise ValueError(f"states must hold a positive multiple of {t} elements, not {states.numel()}")
+        self._check_matrix_device(states, "states")
+        _L.check(self._lib.ntt_poseidon2_permute(self._h, C.c_void_p(states.data_ptr()), states.numel() // t,
+                                                 _stream_ptr(stream, states.device)), "ntt_poseidon2_permute")
+        return states
+
+    def merkle_commit(self, mat: torch.Tensor, width: int, tree: torch.Tensor, *, log_rows: Optional[int] = None,
+                      stream=None) -> torch.Tensor:
+        """``tree`` = [2N - 1][D] receives the Poseidon2 Merkle tree over the N = 2^log_rows rows of ``mat`` =
+        [N][width] (ntt_merkle_commit): the leaf digests first, in row order, the root last."""
+        log_rows = self._check_hash_call(width, log_rows)
+        rows, d = 1 << log_rows, self.poseidon2_width // 2
+        self._check_deep_matrix(mat, rows, width)
+        self._check_matrix(tree, 2 * rows - 1, d, "tree")
+        eb = self.elem_bytes
+        self._check_no_overlap(tree, "tree", (2 * rows - 1) * d * eb, ((mat, "mat", rows * width * eb),))
+        for t, what in ((mat, "mat"), (tree, "tree")):
+            self._check_matrix_device(t, what)
+        _L.check(self._lib.ntt_merkle_commit(self._h, C.c_void_p(mat.data_ptr()), int(width), int(log_rows),
+                                             C.c_void_p(tree.data_ptr()), _stream_ptr(stream, tree.device)),
+                 "ntt_merkle_commit")
+        return tree
+
+    def merkle_open(self, mat: Optional[torch.Tensor], width: int, tree: torch.Tensor, index: torch.Tensor,
+                    rows_out: Optional[torch.Tensor], paths: torch.Tensor, *, log_rows: Optional[int] = None,
+                    stream=None):
+        """For every query q of ``index`` (int32, taken & (N - 1)): ``rows_out[q]`` = that row of ``mat`` and
+        ``paths[q][l]`` = the sibling at layer l (ntt_merkle_open).  ``mat`` and ``rows_out`` may both be None."""
+        log_rows = self._check_hash_call(width, log_rows)
+        rows, d = 1 << log_rows, self.poseidon2_width // 2
+        if (mat is None) != (rows_out is None):
+            raise ValueError("mat and rows_out must both be given or both be None")
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or not index.is_contiguous() or index.numel() < 1:
+            raise ValueError("index must be a contiguous int32 tensor of at least one query")
+        nq = index.numel()
+        self._check_matrix(tree, 2 * rows - 1, d, "tree")
+        if log_rows or paths is not None:
+            self._check_matrix(paths, nq * log_rows, d, "paths")
+        eb = self.elem_bytes
+        inputs = [(tree, "tree", (2 * rows - 1) * d * eb), (index, "index", nq * 4)]
+        if mat is not None:
+            self._check_deep_matrix(mat, rows, width)
+            self._check_matrix(rows_out, nq, width, "rows_out")
+            inputs.append((mat, "mat", rows * width * eb))
+            self._check_no_overlap(rows_out, "rows_out", nq * width * eb, inputs)
+        if paths is not None and log_rows:
+            self._check_no_overlap(paths, "paths", nq * log_rows * d * eb, inputs)
+        for t, what in ((mat, "mat"), (tree, "tree"), (index, "index"), (rows_out, "rows_out"), (paths, "paths")):
+            if t is not None:
+                self._check_matrix_device(t, what)
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        _L.check(self._lib.ntt_merkle_open(self._h, ptr(mat), int(width), int(log_rows), ptr(tree), ptr(index), nq,
+                                           ptr(rows_out), ptr(paths), _stream_ptr(stream, tree.device)),
+                 "ntt_merkle_open")
+        return rows_out, paths
+
+    def merkle_info(self, width: int, *, log_rows: Optional[int] = None):
+        """(digest_elems, tree_elems, launches, tail_log) of ``merkle_commit`` at this shape (ntt_merkle_info)."""
+        self._check_hashing()
+        if log_rows is None:
+            log_rows = self.log_n
+        if not self._is_int(log_rows) or not 0 <= log_rows <= self.log_n:
+            raise ValueError(f"log_rows must be an integer in [0, {self.log_n}], not {log_rows!r}")
+        if not self._is_int(width) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if (width << log_rows) >= 1 << 32:
+            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+        d, te, la, tl = C.c_uint(), C.c_uint64(), C.c_uint(), C.c_uint()
+        _L.check(self._lib.ntt_merkle_info(self._h, int(width), int(log_rows), C.byref(d), C.byref(te), C.byref(la),
+                                           C.byref(tl)), "ntt_merkle_info")
+        return d.value, te.value, la.value, tl.value
+
     def matrix_passes(self, width: int) -> List[int]:
         """log2 radices of the passes the matrix calls run at this width (ntt_plan_matrix_info); [] for
         sizes up to 4 rows, which one simple kernel transforms."""
