@@ -468,6 +468,52 @@ int ntt_merkle_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned 
 int ntt_merkle_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned* digest_elems,
                     uint64_t* tree_elems, unsigned* launches, unsigned* tail_log);
 
+/* Batch inversion and running sums / products down the columns of a row-major matrix: the second trace stage
+ * between the first commitment and the second extension, the LogUp running-sum columns z_{i+1} = z_i + term_i and
+ * the permutation argument's running products z_{i+1} = z_i ratio_i.  An extension element is d = ext_degree in
+ * {1, 2, 4} adjacent base coefficients of F_p[X]/(X^d - W), W = ext_w, as in ntt_fri_fold.  Every buffer is in the
+ * plan's I/O form (Montgomery on NTT_PLAN_MONTGOMERY_IO plans); ext_w is a canonical host word.
+ *   ntt_batch_inverse  d_in, d_out [count][d]: d_out[i] = d_in[i]^-1 in the same form (v R goes to v^-1 R on
+ *     Montgomery plans).  A zero element gives exactly zero and does not disturb its neighbours.  Montgomery's
+ *     trick on runs: a thread multiplies up a run of 32 / d consecutive elements of 4 bytes (16 / d of 8 bytes),
+ *     a zero counting as one, inverts the product once and walks back; the data reach the threads and leave them
+ *     through LDS, 16 bytes a lane.  Where X^d - W is reducible and an element is a nonzero zero divisor, the
+ *     outputs of that element's run are unspecified; nothing faults.  One launch.  d_out == d_in is allowed.
+ *   ntt_matrix_scan  M = d_in = [rows][width] extension elements, row-major without pitch, any rows >= 1 (no table
+ *     of the plan is used: rows may exceed the plan's n).  With (+) the field addition (op == NTT_SCAN_SUM) or the
+ *     ring product (NTT_SCAN_PRODUCT): d_out[i][j] = (+)_{r <= i} M[r][j]; with flags & NTT_SCAN_EXCLUSIVE
+ *     d_out[i][j] = (+)_{r < i} M[r][j] and d_out[0][j] is the identity: 0 for the sum; for the product 1 in the
+ *     plan's I/O form in coordinate 0.  d_totals [width][d] (may be NULL) receives (+)_{all r} M[r][j] in both
+ *     modes.  For the sum ext_w is ignored and the call is the scan of width d base columns.  Three launches:
+ *     strips of adjacent columns x chunks of rows reduce into a plan-owned buffer [chunk][column][d] (allocated
+ *     at the first use, its size independent of rows); the exclusive scan of the chunk aggregates per column and
+ *     the totals; the chunks again, each scanned from its prefix.  One launch when there is one chunk.  Rows of
+ *     at least 64 bytes: a strip is a power of two of columns, 64 to 256 bytes of a row.  Shorter rows: a chunk
+ *     is one contiguous byte range that goes through LDS, 16 bytes a lane.  No atomics and no wait of one
+ *     workgroup on another: the same bits every run.  d_out == d_in is allowed.
+ *   ntt_scan_info  the decisions at (rows, width, ext_degree, op): the columns of a strip (for the sum: of the
+ *     width d base columns), the consecutive rows a thread holds, the rows of a chunk, the chunks and the
+ *     launches.  No launch.
+ * The two launching calls are asynchronous on hip_stream and never synchronise the host.  Any element-aligned
+ * pointer is accepted; 16-byte accesses are used when the pointers are 16-byte aligned and the buffers whole
+ * 16-byte words long.
+ * Engines: as the matrix calls; plans of fields 0-2 and of custom 4- and 6-limb moduli return NTT_ERR_ARG.
+ * NTT_ERR_ARG before any launch, the buffers untouched: a null plan or pointer (d_totals may be NULL), count, rows
+ * or width 0, count d or rows width d >= 2^32, ext_degree outside {1, 2, 4}, ext_w 0 or >= p when it is read
+ * (ext_degree > 1, and not for the sum), an unknown op or flag bit, NTT_PLAN_TWIDDLE_ONLY plans, d_out overlapping
+ * d_in other than d_out == d_in, d_totals overlapping d_in or d_out. */
+#define NTT_SCAN_SUM 0u
+#define NTT_SCAN_PRODUCT 1u
+#define NTT_SCAN_EXCLUSIVE 1u
+int ntt_batch_inverse(ntt_plan* plan, const void* d_in, void* d_out, uint64_t count, unsigned ext_degree,
+                      uint64_t ext_w, void* hip_stream);
+int ntt_matrix_scan(ntt_plan* plan, const void* d_in, void* d_out, uint64_t rows, unsigned width,
+                    unsigned ext_degree, uint64_t ext_w, unsigned op, unsigned flags, void* d_totals,
+                    void* hip_stream);
+int ntt_scan_info(const ntt_plan* plan, uint64_t rows, unsigned width, unsigned ext_degree, unsigned op,
+                  unsigned* strip_cols, unsigned* run_rows, unsigned* chunk_rows, unsigned* chunks,
+                  unsigned* launches);
+
 /* Pointwise product c = a * b mod p over 2^log_n elements (polynomial-multiply middle step);
  * a b R^-1 with NTT_PLAN_MONTGOMERY_IO. */
 int ntt_pointwise_mul(ntt_plan* plan, const void* d_a, const void* d_b, void* d_c, void* hip_stream);
@@ -530,7 +576,8 @@ int ntt_plan_last_launch_ms(ntt_plan* plan, float* ms, unsigned max_launches, un
  * d digit-reversal swap; b single launch; n naive; x FRI fold, with log_arity for the radix; z DEEP points;
  * o open: strip sums, e open: the chunks and the scalars; a quotient: the alpha table, q quotient: the rows), ""
  * when unlabelled.  The Merkle calls: h leaf hash; m tree layers, with the number of layers the launch covers for
- * the radix; g open (gather); p permute.  NTT_ERR_ARG when `cap`
+ * the radix; g open (gather); p permute.  The inverse and the scans: v batch inverse; t chunk totals, k the scan
+ * of the totals, y the chunk scan.  NTT_ERR_ARG when `cap`
  * bytes do not hold them.  New (round 6): benchmarks pair per-launch PMC bytes with launches by
  * label, not by position. */
 int ntt_plan_last_launch_labels(ntt_plan* plan, char* buf, unsigned cap);

@@ -47,6 +47,7 @@ SOURCES += ["ntt_eg_mat.hip", "ntt_e31_mat.hip"]  # row-major matrix passes, the
 SOURCES += ["ntt_eg_fold.hip", "ntt_e31_fold.hip"]  # FRI fold of bit-reversed coset evaluations (ntt_fri_fold)
 SOURCES += ["ntt_eg_deep.hip", "ntt_e31_deep.hip"]  # DEEP openings and quotients of evaluation matrices (ntt_deep_*, ntt_matrix_open)
 SOURCES += ["ntt_eg_hash.hip", "ntt_e31_hash.hip"]  # Poseidon2 Merkle commitments and openings (ntt_poseidon2_permute, ntt_merkle_*)
+SOURCES += ["ntt_eg_scan.hip", "ntt_e31_scan.hip"]  # batch inversion, running sums and products down matrix columns (ntt_batch_inverse, ntt_matrix_scan)
 SOURCES += ["ntt_plan.cpp", "ntt_rplan.cpp", "ntt_multi.cpp"]
 ARCH = os.environ.get("NTT_OFFLOAD_ARCH", "gfx950")
 

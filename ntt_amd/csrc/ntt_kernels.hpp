@@ -7,6 +7,7 @@
 #include "fieldext.hpp"
 #include "plan_fused.hpp"
 #include "poseidon2.hpp"
+#include "scan_shape.hpp"
 
 namespace ntt {
 
@@ -516,6 +517,40 @@ hipError_t launch_merkle_tail(unsigned sbox_degree, uint32_t* tree, const deep_v
 template <class E>
 hipError_t launch_merkle_open(const uint32_t* mat, const uint32_t* tree, const uint32_t* index, uint32_t* rows,
                               uint32_t* paths, const HashArgs<E>& A, hipStream_t st);
+
+// ---- batch inversion and running sums / products down the columns of a row-major matrix (ntt_batch_inverse,
+// ntt_matrix_scan; kernels in ntt_scan_impl.hpp, instances in ntt_eg_scan.hip and ntt_e31_scan.hip: the HasMat
+// engines).  The shape decisions: scan_shape.hpp (ScanShape, InvShape).
+template <class E>
+struct ScanArgs {
+  deep_k_t<E> K;          // the field's constants with W
+  uint32_t* dbg;          // checked build: the plan's status word
+  deep_val_t<E> ident;    // coordinate 0 of the operation's identity in the plan's I/O form
+  deep_val_t<E> r2;       // conv: 2^64 mod p, which brings a canonical value to the working form by one product
+  deep_val_t<E> rinv;     // conv: 2^-32 mod p, which brings the inverse of a run's product to the canonical form
+  uint32_t conv;          // 4-byte canonical plans: one operand of every product goes to the working form first
+  uint32_t vec;           // the caller's buffers are 16-byte aligned and whole 16-byte words long: vector access
+  uint32_t excl;          // scan: NTT_SCAN_EXCLUSIVE
+  uint32_t mid_cols, mid_run;  // scan, second launch (ScanShape::mid_cols, mid_run)
+  ScanShape S;            // scan: the shape
+  uint64_t rows;          // scan
+  uint64_t count;         // inverse: elements
+  size_t io_elems, buf_elems, tot_elems;  // checked build: base elements of d_in / d_out, the plan's buffer, d_totals
+};
+// inverse: d_in, d_out [count][d], form < InvShape::FORMS.  scan: the three launches; prod: the ring product of
+// degree-d elements, else the sum, whose d is 1 (the caller folds the degree into the columns).  reduce: in ->
+// buf [chunk][column][d]; mid: buf -> its exclusive scan in place, and totals (null: none); chunk: in, buf -> out,
+// and totals when the shape has one chunk (buf is then not read).
+template <class E>
+hipError_t launch_batch_inverse(unsigned d, unsigned form, const uint32_t* in, uint32_t* out, const ScanArgs<E>& A,
+                                hipStream_t st);
+template <class E>
+hipError_t launch_scan_reduce(unsigned d, bool prod, const uint32_t* in, uint32_t* buf, const ScanArgs<E>& A, hipStream_t st);
+template <class E>
+hipError_t launch_scan_mid(unsigned d, bool prod, uint32_t* buf, uint32_t* totals, const ScanArgs<E>& A, hipStream_t st);
+template <class E>
+hipError_t launch_scan_chunk(unsigned d, bool prod, const uint32_t* in, uint32_t* out, const uint32_t* buf, uint32_t* totals,
+                             const ScanArgs<E>& A, hipStream_t st);
 
 template <class E>
 hipError_t launch_build_tw(uint32_t* out, size_t count, uint32_t log_r, uint32_t log_t, uint32_t log_m,

@@ -93,6 +93,7 @@ struct FirstPass {
 #include "plan_hash.hpp"    // Hash<E, Plan>: Poseidon2 Merkle commitments and openings
 #include "plan_matrix.hpp"  // Matrix<E, Plan>: the row-major matrix transforms
 #include "plan_rivals.hpp"  // Rivals<E, Plan>: the rival schedules
+#include "plan_scan.hpp"    // Scan<E, Plan>: batch inversion, running sums and products down matrix columns
 #include "plan_shift.hpp"   // Shift<E, Plan>: the shift cache, coset transforms, low-degree extension
 #include "plan_single.hpp"  // Single<E, Plan>: the single-launch schedules, the in-place final pass
 
@@ -164,6 +165,14 @@ struct PlanBase {
                           unsigned nq, void* rows, void* paths, hipStream_t st) = 0;
   virtual int merkle_info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems,
                           unsigned* launches, unsigned* tail_log) const = 0;
+  // batch inversion and running sums / products down the columns of a row-major matrix (ntt_batch_inverse,
+  // ntt_matrix_scan, ntt_scan_info)
+  virtual int batch_inverse(const void* in, void* out, uint64_t count, unsigned ext_degree, uint64_t ext_w,
+                            hipStream_t st) = 0;
+  virtual int matrix_scan(const void* in, void* out, uint64_t rows, unsigned width, unsigned ext_degree, uint64_t ext_w,
+                          unsigned op, unsigned fl, void* totals, hipStream_t st) = 0;
+  virtual int scan_info(uint64_t rows, unsigned width, unsigned ext_degree, unsigned op, unsigned* strip_cols,
+                        unsigned* run_rows, unsigned* chunk_rows, unsigned* chunks, unsigned* launches) const = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -288,6 +297,7 @@ struct PlanImpl final : PlanBase {
   Fold<E, PlanImpl> folder{*this};    // FRI fold (plan_fold.hpp)
   Deep<E, PlanImpl> deep{*this};      // DEEP openings and quotients (plan_deep.hpp)
   Hash<E, PlanImpl> hash{*this};      // Poseidon2 Merkle commitments and openings (plan_hash.hpp)
+  Scan<E, PlanImpl> scanner{*this};   // batch inversion, running sums and products (plan_scan.hpp)
   Single<E, PlanImpl> single{*this};  // single-launch schedules, the in-place final pass (plan_single.hpp)
   unsigned lo_bits = 0;
   uint32_t nrand = 1, top_bits = 28;
@@ -691,6 +701,17 @@ struct PlanImpl final : PlanBase {
   int merkle_info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems, unsigned* launches,
                   unsigned* tail_log) const override {
     return hash.info(width, log_rows, digest_elems, tree_elems, launches, tail_log);
+  }
+  int batch_inverse(const void* in, void* out, uint64_t count, unsigned ext_degree, uint64_t ext_w, hipStream_t st) override {
+    return scanner.inverse(in, out, count, ext_degree, ext_w, st);
+  }
+  int matrix_scan(const void* in, void* out, uint64_t rows, unsigned width, unsigned ext_degree, uint64_t ext_w, unsigned op,
+                  unsigned fl, void* totals, hipStream_t st) override {
+    return scanner.scan(in, out, rows, width, ext_degree, ext_w, op, fl, totals, st);
+  }
+  int scan_info(uint64_t rows, unsigned width, unsigned ext_degree, unsigned op, unsigned* strip_cols, unsigned* run_rows,
+                unsigned* chunk_rows, unsigned* chunks, unsigned* launches) const override {
+    return scanner.info(rows, width, ext_degree, op, strip_cols, run_rows, chunk_rows, chunks, launches);
   }
   bool single_launch_ready() override { return single.ready(); }
 
@@ -1443,6 +1464,26 @@ int ntt_merkle_info(const ntt_plan* plan, unsigned width, unsigned log_rows, uns
                     unsigned* launches, unsigned* tail_log) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;
   return plan->impl->merkle_info(width, log_rows, digest_elems, tree_elems, launches, tail_log);
+}
+// Batch inversion and running sums / products: the plan's own engine (never the second plan)
+int ntt_batch_inverse(ntt_plan* plan, const void* d_in, void* d_out, uint64_t count, unsigned ext_degree, uint64_t ext_w,
+                      void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.batch_inverse(d_in, d_out, count, ext_degree, ext_w, S(s));
+  });
+}
+int ntt_matrix_scan(ntt_plan* plan, const void* d_in, void* d_out, uint64_t rows, unsigned width, unsigned ext_degree,
+                    uint64_t ext_w, unsigned op, unsigned flags, void* d_totals, void* s) {
+  return on_device(plan, [&](PlanBase& P) {
+    plan->last = &P;
+    return P.matrix_scan(d_in, d_out, rows, width, ext_degree, ext_w, op, flags, d_totals, S(s));
+  });
+}
+int ntt_scan_info(const ntt_plan* plan, uint64_t rows, unsigned width, unsigned ext_degree, unsigned op,
+                  unsigned* strip_cols, unsigned* run_rows, unsigned* chunk_rows, unsigned* chunks, unsigned* launches) {
+  if (!plan || !plan->impl) return NTT_ERR_ARG;
+  return plan->impl->scan_info(rows, width, ext_degree, op, strip_cols, run_rows, chunk_rows, chunks, launches);
 }
 int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
   if (!plan || !plan->impl) return NTT_ERR_ARG;

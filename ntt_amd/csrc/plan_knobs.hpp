@@ -67,6 +67,11 @@ inline const char* schedule() { return Env("NTT_SCHEDULE").text(); }
 // own fibre (A/B); unset or empty (-1): the plan's default form
 inline int fold_staged() { return (int)Env("NTT_FOLD_STAGED").num(-1); }
 
+// ---- at every ntt_batch_inverse call (tools/bench_scan.py times the forms interleaved in one process)
+// NTT_INV_FORM=0 / 1 / 2: how k_batch_inv shares an inversion (scan_shape.hpp InvShape: a run of 16 words, of 32,
+// or one inversion per wave; A/B); unset or empty (-1): the default form
+inline int inv_form() { return (int)Env("NTT_INV_FORM").num(-1); }
+
 // ---- when a plan first builds its single-launch or in-place state
 // NTT_FUSED_MODE=0: the dataflow form of k_fused3 (per-tile hand-offs), else the grid-barrier form (1)
 inline unsigned fused_mode() { return Env("NTT_FUSED_MODE").is('0') ? 0u : 1u; }

@@ -38,6 +38,9 @@ NTT_PLAN_ELEM32 = 8192
 NTT_MATRIX_BITREV_OUT = 1
 NTT_MATRIX_BITREV_IN = 2
 NTT_DEEP_ACCUMULATE = 1
+NTT_SCAN_SUM = 0
+NTT_SCAN_PRODUCT = 1
+NTT_SCAN_EXCLUSIVE = 1
 
 # Every symbol declared in include/ntt.h with its ctypes prototype: (restype, argtypes).
 _vp = C.c_void_p
@@ -76,6 +79,10 @@ PROTOTYPES = {
     "ntt_merkle_open": (C.c_int, [_vp, _vp, C.c_uint, C.c_uint, _vp, _vp, C.c_uint, _vp, _vp, _vp]),
     "ntt_merkle_info": (C.c_int, [_vp, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint64),
                                   C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "ntt_batch_inverse": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint, C.c_uint64, _vp]),
+    "ntt_matrix_scan": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint, C.c_uint, C.c_uint64, C.c_uint, C.c_uint, _vp, _vp]),
+    "ntt_scan_info": (C.c_int, [_vp, C.c_uint64, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "ntt_polymul": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ntt_fill": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, _vp]),
     "ntt_plan_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint), C.POINTER(C.c_uint),

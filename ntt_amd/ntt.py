@@ -712,6 +712,108 @@ class NTTPlan:
                                            C.byref(tl)), "ntt_merkle_info")
         return d.value, te.value, la.value, tl.value
 
+    # -------------------------------------------------------------------------------- batch inverse and column scans
+    def _check_scan_engine(self) -> None:
+        if not self.poseidon2_width:  # the engines of the matrix calls
+            raise ValueError("batch_inverse and matrix_scan need a Goldilocks plan or a plan of 4-byte elements")
+
+    def _check_ext(self, ext_degree, ext_w, reads_w=True) -> None:
+        if not self._is_int(ext_degree) or ext_degree not in (1, 2, 4):
+            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
+        if reads_w and ext_degree > 1 and (not self._is_int(ext_w) or not 0 < ext_w < self.p):
+            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
+
+    def _check_flat(self, t, name) -> None:
+        if not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.dtype != self.dtype:
+            raise ValueError(f"{name} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the plan's "
+                             "element layout")
+
+    def _check_same_or_apart(self, a, a_name, b, b_name, nbytes) -> None:
+        a0, b0 = a.data_ptr(), b.data_ptr()
+        if a0 != b0 and a0 < b0 + nbytes and b0 < a0 + nbytes:
+            raise ValueError(f"{a_name} and {b_name} overlap (they may be the same buffer, or apart)")
+
+    def batch_inverse(self, t: torch.Tensor, out: Optional[torch.Tensor] = None, *, ext_degree: int = 1, ext_w: int = 0,
+                      stream=None) -> torch.Tensor:
+        """``out`` = [count][ext_degree] receives the inverse of every element of ``t`` in the plan's I/O form
+        (ntt_batch_inverse); a zero element gives zero.  ``out`` None: in place."""
+        self._check_scan_engine()
+        self._check_ext(ext_degree, ext_w)
+        self._check_flat(t, "t")
+        out = t if out is None else out
+        self._check_flat(out, "out")
+        elems = t.numel() * t.element_size() // self.elem_bytes
+        if elems == 0 or elems % ext_degree:
+            raise ValueError(f"t must hold a positive multiple of {ext_degree} elements, not {elems}")
+        if elems >= 1 << 32:
+            raise ValueError(f"count * ext_degree must stay below 2^32, not {elems}")
+        if out.numel() != t.numel():
+            raise ValueError(f"out: expected {t.numel()} elements like t, not {out.numel()}")
+        self._check_same_or_apart(t, "t", out, "out", elems * self.elem_bytes)
+        for x, what in ((t, "t"), (out, "out")):
+            self._check_matrix_device(x, what)
+        _L.check(self._lib.ntt_batch_inverse(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             elems // ext_degree, int(ext_degree), int(ext_w) if ext_degree > 1 else 0,
+                                             _stream_ptr(stream, out.device)), "ntt_batch_inverse")
+        return out
+
+    def _check_scan_shape(self, width, ext_degree, ext_w, op, rows) -> int:
+        """The arguments matrix_scan and scan_info share.  Returns the op's number."""
+        self._check_scan_engine()
+        if op not in ("sum", "product"):
+            raise ValueError(f"op must be 'sum' or 'product', not {op!r}")
+        self._check_ext(ext_degree, ext_w, reads_w=op == "product")
+        if not self._is_int(width) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if not self._is_int(rows) or rows < 1:
+            raise ValueError(f"rows must be a positive integer, not {rows!r}")
+        if rows * width * ext_degree >= 1 << 32:
+            raise ValueError(f"rows * width * ext_degree must stay below 2^32, not {rows} * {width} * {ext_degree}")
+        return _L.NTT_SCAN_PRODUCT if op == "product" else _L.NTT_SCAN_SUM
+
+    def matrix_scan(self, mat: torch.Tensor, out: torch.Tensor, width: int, *, op: str = "sum", exclusive: bool = False,
+                    totals: Optional[torch.Tensor] = None, ext_degree: int = 1, ext_w: int = 0,
+                    rows: Optional[int] = None, stream=None) -> torch.Tensor:
+        """``out[i][j]`` = the sum (``op`` "sum") or ring product ("product") of ``mat[r][j]`` over r <= i
+        (``exclusive``: r < i, row 0 the identity) for ``mat`` = [rows][width] elements of ``ext_degree`` coefficients
+        (ntt_matrix_scan); ``totals`` = [width][ext_degree] receives the columns' totals.  ``out`` may be ``mat``.
+        ``rows`` defaults to what ``mat`` holds."""
+        self._check_flat(mat, "mat")
+        if rows is None and self._is_int(width) and width > 0 and self._is_int(ext_degree) and ext_degree in (1, 2, 4):
+            rows = mat.numel() * mat.element_size() // (self.elem_bytes * width * ext_degree)
+        opn = self._check_scan_shape(width, ext_degree, ext_w, op, rows)
+        if not isinstance(exclusive, bool):
+            raise ValueError(f"exclusive must be a bool, not {exclusive!r}")
+        self._check_flat(out, "out")
+        elems = rows * width * ext_degree
+        for x, what in ((mat, "mat"), (out, "out")):
+            if x.numel() * x.element_size() != elems * self.elem_bytes:
+                raise ValueError(f"{what}: expected {rows} rows of {width * ext_degree} elements of {self.elem_bytes} bytes")
+        self._check_same_or_apart(mat, "mat", out, "out", elems * self.elem_bytes)
+        if totals is not None:
+            self._check_flat(totals, "totals")
+            if totals.numel() * totals.element_size() != width * ext_degree * self.elem_bytes:
+                raise ValueError(f"totals: expected {width} rows of {ext_degree} elements of {self.elem_bytes} bytes")
+            self._check_no_overlap(totals, "totals", width * ext_degree * self.elem_bytes,
+                                   ((mat, "mat", elems * self.elem_bytes), (out, "out", elems * self.elem_bytes)))
+        for x, what in ((mat, "mat"), (out, "out"), (totals, "totals")):
+            if x is not None:
+                self._check_matrix_device(x, what)
+        _L.check(self._lib.ntt_matrix_scan(self._h, C.c_void_p(mat.data_ptr()), C.c_void_p(out.data_ptr()), int(rows),
+                                           int(width), int(ext_degree), int(ext_w) if ext_degree > 1 and opn else 0, opn,
+                                           _L.NTT_SCAN_EXCLUSIVE if exclusive else 0,
+                                           None if totals is None else C.c_void_p(totals.data_ptr()),
+                                           _stream_ptr(stream, out.device)), "ntt_matrix_scan")
+        return out
+
+    def scan_info(self, rows: int, width: int, *, op: str = "sum", ext_degree: int = 1):
+        """(strip_cols, run_rows, chunk_rows, chunks, launches) of ``matrix_scan`` at this shape (ntt_scan_info)."""
+        opn = self._check_scan_shape(width, ext_degree, 1, op, rows)
+        v = [C.c_uint() for _ in range(5)]
+        _L.check(self._lib.ntt_scan_info(self._h, int(rows), int(width), int(ext_degree), opn, *(C.byref(x) for x in v)),
+                 "ntt_scan_info")
+        return tuple(x.value for x in v)
+
     def matrix_passes(self, width: int) -> List[int]:
         """log2 radices of the passes the matrix calls run at this width (ntt_plan_matrix_info); [] for
         sizes up to 4 rows, which one simple kernel transforms."""
