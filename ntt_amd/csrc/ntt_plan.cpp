@@ -88,18 +88,18 @@ struct FirstPass {
 }  // namespace
 
 // the plan's features, each a struct the plan owns and hands a reference to itself; they name FirstPass
-#include "plan_deep.hpp"    // Deep<E, Plan>: DEEP openings and quotients of evaluation matrices
-#include "plan_fold.hpp"    // Fold<E, Plan>: ntt_fri_fold
-#include "plan_hash.hpp"    // Hash<E, Plan>: Poseidon2 Merkle commitments and openings
-#include "plan_matrix.hpp"  // Matrix<E, Plan>: the row-major matrix transforms
+#include "plan_prover.hpp"  // Prover<E, Plan>: the prover-stage calls (matrix, fold, DEEP, Merkle, scans), HasMat engines only
 #include "plan_rivals.hpp"  // Rivals<E, Plan>: the rival schedules
-#include "plan_scan.hpp"    // Scan<E, Plan>: batch inversion, running sums and products down matrix columns
 #include "plan_shift.hpp"   // Shift<E, Plan>: the shift cache, coset transforms, low-degree extension
 #include "plan_single.hpp"  // Single<E, Plan>: the single-launch schedules, the in-place final pass
 
 namespace {
 
 // ------------------------------------------------------------------------------ plan
+// the address of kEngineTag<E> names engine E (PlanBase::engine)
+template <class E>
+constexpr char kEngineTag = 0;
+
 struct PlanBase {
   // Destruction: ~PlanImpl makes the plan's device current, its DevBuf members free themselves there,
   // and this, which runs last, returns the watchdog slot and the events and restores the caller's device
@@ -111,6 +111,7 @@ struct PlanBase {
     if (caller_device >= 0) (void)hipSetDevice(caller_device);
   }
   int caller_device = -1;  // set by ~PlanImpl
+  const void* engine = nullptr;  // &kEngineTag<E> of the PlanImpl<E> this is
   virtual int run(void* d, unsigned batch, bool inverse, hipStream_t st) = 0;
   virtual int pointwise(const void* a, const void* b, void* c, hipStream_t st) = 0;
   virtual int polymul(void* a, void* b, void* c, hipStream_t st) = 0;
@@ -134,45 +135,6 @@ struct PlanBase {
   // low-degree extension (ntt_lde_batch): batch inputs of n >> log_blowup coefficients to batch outputs of n
   virtual int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* shift, unsigned limbs64,
                   unsigned batch, hipStream_t st) = 0;
-  // the columns of a row-major [n][width] matrix (ntt_forward_matrix / ntt_inverse_matrix: in == out;
-  // ntt_lde_matrix: is_lde, in = [n >> log_blowup][width]) and the schedule those calls run
-  // order: NTT_MATRIX_BITREV_* (the _ex calls); shift: the lde's and the _ex calls' coset, null: c = 1
-  virtual int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
-                     const uint64_t* shift, unsigned limbs64, unsigned order, hipStream_t st) = 0;
-  virtual int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const = 0;
-  // FRI fold of bit-reversed coset evaluations (ntt_fri_fold): [2^log_rows][d] -> [2^(log_rows - log_arity)][d]
-  virtual int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree,
-                   uint64_t ext_w, const uint64_t* beta, const uint64_t* shift, hipStream_t st) = 0;
-  // DEEP openings and quotients of a row-major coset evaluation matrix (ntt_deep_points, ntt_matrix_open,
-  // ntt_deep_quotient, ntt_deep_info)
-  virtual int deep_points(void* inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w, const uint64_t* z,
-                          const uint64_t* shift, unsigned order, hipStream_t st) = 0;
-  virtual int deep_open(const void* mat, unsigned width, unsigned log_rows, const void* inv, unsigned ext_degree,
-                        uint64_t ext_w, const uint64_t* z, const uint64_t* shift, unsigned order, void* values,
-                        hipStream_t st) = 0;
-  virtual int deep_quotient(const void* mat, unsigned width, unsigned log_rows, const void* inv, const void* values,
-                            unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha, const uint64_t* scale,
-                            unsigned flags, void* out, hipStream_t st) = 0;
-  virtual int deep_info(unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
-                        unsigned* quotient_lanes_per_row) const = 0;
-  // Poseidon2 Merkle commitments and openings of a row-major matrix (ntt_plan_set_poseidon2, ntt_poseidon2_permute,
-  // ntt_merkle_commit, ntt_merkle_open, ntt_merkle_info)
-  virtual int poseidon2_set(unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p,
-                            const uint64_t* ext_rc, const uint64_t* int_rc, const uint64_t* int_diag) = 0;
-  virtual int poseidon2_permute(void* states, uint64_t count, hipStream_t st) = 0;
-  virtual int merkle_commit(const void* mat, unsigned width, unsigned log_rows, void* tree, hipStream_t st) = 0;
-  virtual int merkle_open(const void* mat, unsigned width, unsigned log_rows, const void* tree, const uint32_t* index,
-                          unsigned nq, void* rows, void* paths, hipStream_t st) = 0;
-  virtual int merkle_info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems,
-                          unsigned* launches, unsigned* tail_log) const = 0;
-  // batch inversion and running sums / products down the columns of a row-major matrix (ntt_batch_inverse,
-  // ntt_matrix_scan, ntt_scan_info)
-  virtual int batch_inverse(const void* in, void* out, uint64_t count, unsigned ext_degree, uint64_t ext_w,
-                            hipStream_t st) = 0;
-  virtual int matrix_scan(const void* in, void* out, uint64_t rows, unsigned width, unsigned ext_degree, uint64_t ext_w,
-                          unsigned op, unsigned fl, void* totals, hipStream_t st) = 0;
-  virtual int scan_info(uint64_t rows, unsigned width, unsigned ext_degree, unsigned op, unsigned* strip_cols,
-                        unsigned* run_rows, unsigned* chunk_rows, unsigned* chunks, unsigned* launches) const = 0;
   virtual int count_noncanonical(const void* d, uint64_t count, uint64_t* bad, hipStream_t st) = 0;
   virtual int device_status(unsigned* bad) = 0;
   // the plan's batch-1 forward / inverse run as ONE launch (NTT_PLAN_SINGLE_LAUNCH): its single-launch
@@ -259,6 +221,30 @@ static bool schedule_for(unsigned log_n, unsigned* r, unsigned& p) {
 }
 
 template <class E>
+struct PlanImpl;
+
+// The engines whose plans hold a Prover (plan_prover.hpp), named here and nowhere else: the prover-stage entry
+// points of the C ABI find the plan's engine by its tag and call the final class, with no virtual per call.
+template <class... Es>
+struct EngineList {
+  template <class E>
+  static constexpr bool has = (std::is_same_v<E, Es> || ...);
+  static_assert((HasMat<Es>::value && ...), "a Prover needs the engine's prover-stage kernels");
+  // f(the plan's Prover); NTT_ERR_ARG, with f not called, for a plan of any other engine
+  template <class F>
+  static int visit(PlanBase& P, F& f) {
+    int rc = NTT_ERR_ARG;
+    (void)((P.engine == &kEngineTag<Es> && ((rc = f(static_cast<PlanImpl<Es>&>(P).prover)), true)) || ...);
+    return rc;
+  }
+};
+using ProverEngines = EngineList<Eng64G, Eng31>;
+struct NoProver {  // what the other engines' plans hold instead
+  template <class Plan>
+  explicit NoProver(Plan&) {}
+};
+
+template <class E>
 struct PlanImpl final : PlanBase {
   static constexpr int NH = EngHost<E>::NH;
   static constexpr int TW = E::TW;
@@ -293,11 +279,9 @@ struct PlanImpl final : PlanBase {
   // the plan's features, each in a header of its own with a reference to the plan
   Rivals<E, PlanImpl> rivals{*this};  // the rival schedules (plan_rivals.hpp)
   Shift<E, PlanImpl> shift{*this};    // the shift cache, coset transforms, low-degree extension (plan_shift.hpp)
-  Matrix<E, PlanImpl> mat{*this};     // row-major matrix transforms (plan_matrix.hpp)
-  Fold<E, PlanImpl> folder{*this};    // FRI fold (plan_fold.hpp)
-  Deep<E, PlanImpl> deep{*this};      // DEEP openings and quotients (plan_deep.hpp)
-  Hash<E, PlanImpl> hash{*this};      // Poseidon2 Merkle commitments and openings (plan_hash.hpp)
-  Scan<E, PlanImpl> scanner{*this};   // batch inversion, running sums and products (plan_scan.hpp)
+  // the prover-stage calls, on the engines that have their kernels (plan_prover.hpp)
+  static_assert(ProverEngines::has<E> == HasMat<E>::value, "ProverEngines lists the HasMat engines");
+  std::conditional_t<ProverEngines::has<E>, Prover<E, PlanImpl>, NoProver> prover{*this};
   Single<E, PlanImpl> single{*this};  // single-launch schedules, the in-place final pass (plan_single.hpp)
   unsigned lo_bits = 0;
   uint32_t nrand = 1, top_bits = 28;
@@ -309,6 +293,7 @@ struct PlanImpl final : PlanBase {
     return d_tab.get() + (dir && pass == 0 ? off_hi_is : off_hi[dir]);
   }
 
+  PlanImpl() { engine = &kEngineTag<E>; }
   // the members' buffers are freed after this body, with the plan's device current (~PlanBase)
   ~PlanImpl() override {
     (void)hipGetDevice(&caller_device);
@@ -657,61 +642,6 @@ struct PlanImpl final : PlanBase {
   int lde(const void* in, void* out, unsigned log_blowup, const uint64_t* c, unsigned limbs64, unsigned batch,
           hipStream_t st) override {
     return shift.lde(in, out, log_blowup, c, limbs64, batch, st);
-  }
-  int matrix(const void* in, void* out, unsigned width, bool inverse, bool is_lde, unsigned log_blowup,
-             const uint64_t* c, unsigned limbs64, unsigned order, hipStream_t st) override {
-    return mat.run(in, out, width, inverse, is_lde, log_blowup, c, limbs64, order, st);
-  }
-  int matrix_info(unsigned width, unsigned* npasses, unsigned* radix_log) const override {
-    return mat.info(width, npasses, radix_log);
-  }
-  int fold(const void* in, void* out, unsigned log_rows, unsigned log_arity, unsigned ext_degree, uint64_t ext_w,
-           const uint64_t* beta, const uint64_t* c, hipStream_t st) override {
-    return folder.run(in, out, log_rows, log_arity, ext_degree, ext_w, beta, c, st);
-  }
-  int deep_points(void* inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w, const uint64_t* z,
-                  const uint64_t* c, unsigned order, hipStream_t st) override {
-    return deep.points(inv, log_rows, ext_degree, ext_w, z, c, order, st);
-  }
-  int deep_open(const void* m, unsigned width, unsigned log_rows, const void* inv, unsigned ext_degree, uint64_t ext_w,
-                const uint64_t* z, const uint64_t* c, unsigned order, void* values, hipStream_t st) override {
-    return deep.open(m, width, log_rows, inv, ext_degree, ext_w, z, c, order, values, st);
-  }
-  int deep_quotient(const void* m, unsigned width, unsigned log_rows, const void* inv, const void* values,
-                    unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha, const uint64_t* scale, unsigned fl,
-                    void* out, hipStream_t st) override {
-    return deep.quotient(m, width, log_rows, inv, values, ext_degree, ext_w, alpha, scale, fl, out, st);
-  }
-  int deep_info(unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
-                unsigned* quotient_lanes_per_row) const override {
-    return deep.info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
-  }
-  int poseidon2_set(unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p, const uint64_t* ext_rc,
-                    const uint64_t* int_rc, const uint64_t* int_diag) override {
-    return hash.set(width, sbox_degree, rounds_f, rounds_p, ext_rc, int_rc, int_diag);
-  }
-  int poseidon2_permute(void* states, uint64_t count, hipStream_t st) override { return hash.permute(states, count, st); }
-  int merkle_commit(const void* m, unsigned width, unsigned log_rows, void* tree, hipStream_t st) override {
-    return hash.commit(m, width, log_rows, tree, st);
-  }
-  int merkle_open(const void* m, unsigned width, unsigned log_rows, const void* tree, const uint32_t* index, unsigned nq,
-                  void* rows, void* paths, hipStream_t st) override {
-    return hash.open(m, width, log_rows, tree, index, nq, rows, paths, st);
-  }
-  int merkle_info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems, unsigned* launches,
-                  unsigned* tail_log) const override {
-    return hash.info(width, log_rows, digest_elems, tree_elems, launches, tail_log);
-  }
-  int batch_inverse(const void* in, void* out, uint64_t count, unsigned ext_degree, uint64_t ext_w, hipStream_t st) override {
-    return scanner.inverse(in, out, count, ext_degree, ext_w, st);
-  }
-  int matrix_scan(const void* in, void* out, uint64_t rows, unsigned width, unsigned ext_degree, uint64_t ext_w, unsigned op,
-                  unsigned fl, void* totals, hipStream_t st) override {
-    return scanner.scan(in, out, rows, width, ext_degree, ext_w, op, fl, totals, st);
-  }
-  int scan_info(uint64_t rows, unsigned width, unsigned ext_degree, unsigned op, unsigned* strip_cols, unsigned* run_rows,
-                unsigned* chunk_rows, unsigned* chunks, unsigned* launches) const override {
-    return scanner.info(rows, width, ext_degree, op, strip_cols, run_rows, chunk_rows, chunks, launches);
   }
   bool single_launch_ready() override { return single.ready(); }
 
@@ -1368,13 +1298,27 @@ int ntt_lde_batch(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_bl
   });
 }
 
-// Row-major matrix transforms: the plan's own engine on the matrix schedule (never the second plan)
+// The prover-stage calls run on the plan's own engine (never the second plan of 4096-element tiles), through its
+// Prover: f(X) with X the plan's Prover<E, PlanImpl<E>>; NTT_ERR_ARG from a plan whose engine has none.
+// A launching call, on the plan's device like every other and remembered for the profiling readers ...
+extern "C++" template <class F>
+static int on_prover(ntt_plan* plan, F&& f, bool launches = true) {
+  return on_device(plan, [&](PlanBase& P) {
+    if (launches) plan->last = &P;
+    return ProverEngines::visit(P, f);
+  });
+}
+// ... and a question about a shape: no device is touched, ntt_last_error stays as it is
+extern "C++" template <class F>
+static int prover_info(const ntt_plan* plan, F&& f) {
+  if (!plan || !plan->impl) return NTT_ERR_ARG;
+  return ProverEngines::visit(*plan->impl, f);
+}
+
+// Row-major matrix transforms, on the matrix schedule
 static int run_matrix(ntt_plan* plan, const void* in, void* out, unsigned width, bool inverse, bool is_lde,
                       unsigned log_blowup, const uint64_t* shift, unsigned order, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.matrix(in, out, width, inverse, is_lde, log_blowup, shift, 1, order, S(s));
-  });
+  return on_prover(plan, [&](auto& X) { return X.mat.run(in, out, width, inverse, is_lde, log_blowup, shift, 1, order, S(s)); });
 }
 int ntt_forward_matrix(ntt_plan* plan, void* d, unsigned width, void* s) {
   return run_matrix(plan, d, d, width, false, false, 0, nullptr, 0, s);
@@ -1397,97 +1341,80 @@ int ntt_lde_matrix_ex(ntt_plan* plan, const void* d_in, void* d_out, unsigned lo
                       unsigned width, unsigned order, void* s) {
   return run_matrix(plan, d_in, d_out, width, false, true, log_blowup, shift, order, s);
 }
-// FRI fold: the plan's own engine (never the second plan), one launch
+int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
+  return prover_info(plan, [&](auto& X) { return X.mat.info(width, npasses, radix_log); });
+}
+// FRI fold: one launch
 int ntt_fri_fold(ntt_plan* plan, const void* d_in, void* d_out, unsigned log_rows, unsigned log_arity,
                  unsigned ext_degree, uint64_t ext_w, const uint64_t* beta, const uint64_t* shift, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.fold(d_in, d_out, log_rows, log_arity, ext_degree, ext_w, beta, shift, S(s));
+  return on_prover(plan, [&](auto& X) {
+    return X.fold.run(d_in, d_out, log_rows, log_arity, ext_degree, ext_w, beta, shift, S(s));
   });
 }
-// DEEP openings and quotients: the plan's own engine (never the second plan)
+// DEEP openings and quotients
 int ntt_deep_points(ntt_plan* plan, void* d_inv, unsigned log_rows, unsigned ext_degree, uint64_t ext_w,
                     const uint64_t* z, const uint64_t* shift, unsigned order, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.deep_points(d_inv, log_rows, ext_degree, ext_w, z, shift, order, S(s));
-  });
+  return on_prover(plan, [&](auto& X) { return X.deep.points(d_inv, log_rows, ext_degree, ext_w, z, shift, order, S(s)); });
 }
 int ntt_matrix_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_inv,
                     unsigned ext_degree, uint64_t ext_w, const uint64_t* z, const uint64_t* shift, unsigned order,
                     void* d_values, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.deep_open(d_mat, width, log_rows, d_inv, ext_degree, ext_w, z, shift, order, d_values, S(s));
+  return on_prover(plan, [&](auto& X) {
+    return X.deep.open(d_mat, width, log_rows, d_inv, ext_degree, ext_w, z, shift, order, d_values, S(s));
   });
 }
 int ntt_deep_quotient(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_inv,
                       const void* d_values, unsigned ext_degree, uint64_t ext_w, const uint64_t* alpha,
                       const uint64_t* scale, unsigned flags, void* d_out, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.deep_quotient(d_mat, width, log_rows, d_inv, d_values, ext_degree, ext_w, alpha, scale, flags, d_out, S(s));
+  return on_prover(plan, [&](auto& X) {
+    return X.deep.quotient(d_mat, width, log_rows, d_inv, d_values, ext_degree, ext_w, alpha, scale, flags, d_out, S(s));
   });
 }
 int ntt_deep_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned ext_degree, unsigned* open_row_chunks,
                   unsigned* quotient_lanes_per_row) {
-  if (!plan || !plan->impl) return NTT_ERR_ARG;
-  return plan->impl->deep_info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
+  return prover_info(plan, [&](auto& X) {
+    return X.deep.info(width, log_rows, ext_degree, open_row_chunks, quotient_lanes_per_row);
+  });
 }
-// Poseidon2 Merkle commitments and openings: the plan's own engine (never the second plan)
+// Poseidon2 Merkle commitments and openings; setting the parameters launches nothing
 int ntt_plan_set_poseidon2(ntt_plan* plan, unsigned width, unsigned sbox_degree, unsigned rounds_f, unsigned rounds_p,
                            const uint64_t* ext_rc, const uint64_t* int_rc, const uint64_t* int_diag) {
-  return on_device(plan, [&](PlanBase& P) {
-    return P.poseidon2_set(width, sbox_degree, rounds_f, rounds_p, ext_rc, int_rc, int_diag);
-  });
+  return on_prover(plan, [&](auto& X) {
+    return X.hash.set(width, sbox_degree, rounds_f, rounds_p, ext_rc, int_rc, int_diag);
+  }, false);
 }
 int ntt_poseidon2_permute(ntt_plan* plan, void* d_states, uint64_t count, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.poseidon2_permute(d_states, count, S(s));
-  });
+  return on_prover(plan, [&](auto& X) { return X.hash.permute(d_states, count, S(s)); });
 }
 int ntt_merkle_commit(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, void* d_tree, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.merkle_commit(d_mat, width, log_rows, d_tree, S(s));
-  });
+  return on_prover(plan, [&](auto& X) { return X.hash.commit(d_mat, width, log_rows, d_tree, S(s)); });
 }
 int ntt_merkle_open(ntt_plan* plan, const void* d_mat, unsigned width, unsigned log_rows, const void* d_tree,
                     const uint32_t* d_index, unsigned nq, void* d_rows, void* d_paths, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.merkle_open(d_mat, width, log_rows, d_tree, d_index, nq, d_rows, d_paths, S(s));
+  return on_prover(plan, [&](auto& X) {
+    return X.hash.open(d_mat, width, log_rows, d_tree, d_index, nq, d_rows, d_paths, S(s));
   });
 }
 int ntt_merkle_info(const ntt_plan* plan, unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems,
                     unsigned* launches, unsigned* tail_log) {
-  if (!plan || !plan->impl) return NTT_ERR_ARG;
-  return plan->impl->merkle_info(width, log_rows, digest_elems, tree_elems, launches, tail_log);
+  return prover_info(plan, [&](auto& X) { return X.hash.info(width, log_rows, digest_elems, tree_elems, launches, tail_log); });
 }
-// Batch inversion and running sums / products: the plan's own engine (never the second plan)
+// Batch inversion and running sums / products
 int ntt_batch_inverse(ntt_plan* plan, const void* d_in, void* d_out, uint64_t count, unsigned ext_degree, uint64_t ext_w,
                       void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.batch_inverse(d_in, d_out, count, ext_degree, ext_w, S(s));
-  });
+  return on_prover(plan, [&](auto& X) { return X.scan.inverse(d_in, d_out, count, ext_degree, ext_w, S(s)); });
 }
 int ntt_matrix_scan(ntt_plan* plan, const void* d_in, void* d_out, uint64_t rows, unsigned width, unsigned ext_degree,
                     uint64_t ext_w, unsigned op, unsigned flags, void* d_totals, void* s) {
-  return on_device(plan, [&](PlanBase& P) {
-    plan->last = &P;
-    return P.matrix_scan(d_in, d_out, rows, width, ext_degree, ext_w, op, flags, d_totals, S(s));
+  return on_prover(plan, [&](auto& X) {
+    return X.scan.scan(d_in, d_out, rows, width, ext_degree, ext_w, op, flags, d_totals, S(s));
   });
 }
 int ntt_scan_info(const ntt_plan* plan, uint64_t rows, unsigned width, unsigned ext_degree, unsigned op,
                   unsigned* strip_cols, unsigned* run_rows, unsigned* chunk_rows, unsigned* chunks, unsigned* launches) {
-  if (!plan || !plan->impl) return NTT_ERR_ARG;
-  return plan->impl->scan_info(rows, width, ext_degree, op, strip_cols, run_rows, chunk_rows, chunks, launches);
-}
-int ntt_plan_matrix_info(const ntt_plan* plan, unsigned width, unsigned* npasses, unsigned radix_log[8]) {
-  if (!plan || !plan->impl) return NTT_ERR_ARG;
-  return plan->impl->matrix_info(width, npasses, radix_log);
+  return prover_info(plan, [&](auto& X) {
+    return X.scan.info(rows, width, ext_degree, op, strip_cols, run_rows, chunk_rows, chunks, launches);
+  });
 }
 
 int ntt_pointwise_mul(ntt_plan* plan, const void* a, const void* b, void* c, void* s) {

@@ -5,60 +5,23 @@
 // hi) at stride 2^(log_n - log_rows), so no table is built and the shift cache of the other calls stays as it
 // is.  The one buffer the calls own holds the open's per-chunk sums or the quotient's scale alpha^j table; it is
 // allocated at the first call that needs it and grows with the width, never with N.
-// A plan owns one Deep and hands it a reference to itself.  Included by ntt_plan.cpp alone.
+// A Prover (plan_prover.hpp) owns one Deep and hands it a reference to itself: X, whose checks and field
+// constants the calls share with the other features, and through it the plan P.  Included by plan_prover.hpp alone.
 #pragma once
-#include <cstring>
-
-#include "ntt_kernels.hpp"
-#include "plan_devmem.hpp"
-#include "plan_hostmath.hpp"
-#include "plan_schedule.hpp"
 
 namespace {
 
 template <class E, class Plan>
 struct Deep {
-  static constexpr int NH = EngHost<E>::NH, MEMW = E::MEMW;
+  static constexpr int MEMW = E::MEMW;
+  using V = deep_val_t<E>;
+  Prover<E, Plan>& X;
   Plan& P;
   DevBuf d_scr;  // open: [chunk][d + 1][width] sums; quotient: V, then the table [width][d]
-  explicit Deep(Plan& plan) : P(plan) {}
+  explicit Deep(Prover<E, Plan>& prover) : X(prover), P(prover.P) {}
 
-  // the checks every call shares and the field's constants; false: NTT_ERR_ARG
-  template <class K>
-  bool common(unsigned log_rows, unsigned d, uint64_t ext_w, K& k) const {
-    if (P.flags & NTT_PLAN_TWIDDLE_ONLY) return false;
-    if (log_rows > P.log_n || log_rows > 32) return false;
-    if (d != 1 && d != 2 && d != 4) return false;
-    if (d > 1 && (ext_w == 0 || !canon(ext_w))) return false;
-    const uint64_t w = d > 1 ? ext_w : 0;
-    if constexpr (std::is_same_v<E, Eng31>) {
-      k.p = P.H.M.p[0];
-      k.pinv = f31::pinv32(k.p);
-      k.one = (uint32_t)((1ull << 32) % k.p);
-      k.w = (uint32_t)w;
-      k.ws = f31::shoup_companion(k.w, k.p);
-    } else {
-      k.one = 1;
-      k.w = w;
-    }
-    return true;
-  }
-  bool canon(uint64_t v) const {
-    if constexpr (std::is_same_v<E, Eng31>) return v < P.H.M.p[0];
-    else return v < kGoldilocksP;
-  }
-  // d canonical host words -> working form; false: a word is not canonical
-  template <class V, class K>
-  bool words(const uint64_t* src, unsigned d, V (&dst)[4], const K& k) const {
-    for (unsigned j = 0; j < 4; ++j) dst[j] = 0;
-    for (unsigned j = 0; j < d; ++j) {
-      if (!canon(src[j])) return false;
-      dst[j] = xf::to_work(src[j], k);
-    }
-    return true;
-  }
   // z^N and c^N (working form); false: z is a base-field point of the coset c<w_N> (z_0^N = c^N)
-  template <class V, class K>
+  template <class K>
   bool off_domain(const V (&z)[4], unsigned d, V c, unsigned log_rows, const K& k, V (&zn)[4], V& cn) const {
     const uint64_t n = 1ull << log_rows;
     V c1[1] = {c}, cn1[1];
@@ -81,23 +44,6 @@ struct Deep {
     const bool base = z[1] == 0 && z[2] == 0 && z[3] == 0;
     return !(base && zn[0] == cn);
   }
-  // shift -> c (working form) and its twiddle; false: not canonical or zero
-  template <class V, class K>
-  bool shift_of(const uint64_t* shift, const K& k, V& c, typename E::Tw* tw) const {
-    const uint64_t cv = shift ? *shift : 1;
-    if (cv == 0 || !canon(cv)) return false;
-    c = xf::to_work(cv, k);
-    if (tw) {
-      Vec<NH> cc{};
-      cc[0] = (uint32_t)cv;
-      if (NH > 1) cc[1] = (uint32_t)(cv >> 32);
-      uint32_t enc[E::TW];
-      P.EH.encode(cc, enc);
-      static_assert(sizeof(typename E::Tw) == E::TW * 4, "a twiddle is its table entry");
-      memcpy(tw, enc, sizeof *tw);
-    }
-    return true;
-  }
   DeepArgs<E> base_args(unsigned log_rows, unsigned width, const deep_k_t<E>& k) const {
     DeepArgs<E> A{};
     A.F = P.Ff;
@@ -106,143 +52,112 @@ struct Deep {
     A.width = width;
     return A;
   }
-  static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-  }
 
   int points(void* inv, unsigned log_rows, unsigned d, uint64_t ext_w, const uint64_t* z, const uint64_t* shift,
              unsigned order, hipStream_t st) {
-    if constexpr (!HasMat<E>::value) {
+    deep_k_t<E> k{};
+    if (!inv || !z || (order & ~NTT_MATRIX_BITREV_OUT) || log_rows > P.log_n || log_rows > 32 ||
+        !X.ext_constants(d, ext_w, k))
       return NTT_ERR_ARG;
-    } else {
-      using V = deep_val_t<E>;
-      deep_k_t<E> k{};
-      if (!inv || !z || (order & ~NTT_MATRIX_BITREV_OUT) || !common(log_rows, d, ext_w, k)) return NTT_ERR_ARG;
-      V zw[4], zn[4], c, cn;
-      typename E::Tw ctw;
-      if (!words(z, d, zw, k) || !shift_of(shift, k, c, &ctw) || !off_domain(zw, d, c, log_rows, k, zn, cn))
-        return NTT_ERR_ARG;
-      DeepArgs<E> A = base_args(log_rows, 0, k);
-      const size_t n = (size_t)1 << log_rows;
-      A.inv_elems = n * d;
-      A.vec = aligned16(inv) && (n * d * MEMW) % 4 == 0;
-      A.lo_s = P.outer_lo(0);
-      A.hi = P.outer_hi(0, 1);
-      A.lo_bits = P.lo_bits;
-      A.tab_shift = P.log_n - log_rows;
-      A.bitrev = order & NTT_MATRIX_BITREV_OUT ? 1u : 0u;
-      A.c = ctw;
-      for (unsigned j = 0; j < 4; ++j) A.z[j] = zw[j];
-      P.begin(st);
-      const hipError_t e = launch_deep_points<E>(d, static_cast<uint32_t*>(inv), A, st);
-      P.mark(st, "z");
-      return Plan::rc_of(e);
-    }
-  }
-
-  // width and N width < 2^32
-  static bool shape_ok(unsigned width, unsigned log_rows) {
-    return width != 0 && log_rows < 32 && ((uint64_t)width << log_rows) < (1ull << 32);
+    V zw[4], zn[4], c, cn;
+    typename E::Tw ctw;
+    if (!X.words(z, d, zw, k) || !X.shift_of(shift, k, c, &ctw) || !off_domain(zw, d, c, log_rows, k, zn, cn))
+      return NTT_ERR_ARG;
+    DeepArgs<E> A = base_args(log_rows, 0, k);
+    const size_t n = (size_t)1 << log_rows;
+    A.inv_elems = n * d;
+    A.vec = aligned16(inv) && (n * d * MEMW) % 4 == 0;
+    A.lo_s = P.outer_lo(0);
+    A.hi = P.outer_hi(0, 1);
+    A.lo_bits = P.lo_bits;
+    A.tab_shift = P.log_n - log_rows;
+    A.bitrev = order & NTT_MATRIX_BITREV_OUT ? 1u : 0u;
+    A.c = ctw;
+    for (unsigned j = 0; j < 4; ++j) A.z[j] = zw[j];
+    P.begin(st);
+    const hipError_t e = launch_deep_points<E>(d, static_cast<uint32_t*>(inv), A, st);
+    P.mark(st, "z");
+    return Plan::rc_of(e);
   }
 
   int open(const void* mat, unsigned width, unsigned log_rows, const void* inv, unsigned d, uint64_t ext_w,
            const uint64_t* z, const uint64_t* shift, unsigned order, void* values, hipStream_t st) {
-    if constexpr (!HasMat<E>::value) {
+    deep_k_t<E> k{};
+    if (!mat || !inv || !values || !z || (order & ~NTT_MATRIX_BITREV_OUT) || !X.shape_ok(width, log_rows) ||
+        !X.ext_constants(d, ext_w, k))
       return NTT_ERR_ARG;
-    } else {
-      using V = deep_val_t<E>;
-      deep_k_t<E> k{};
-      if (!mat || !inv || !values || !z || (order & ~NTT_MATRIX_BITREV_OUT) || !shape_ok(width, log_rows) ||
-          !common(log_rows, d, ext_w, k))
-        return NTT_ERR_ARG;
-      V zw[4], zn[4], c, cn;
-      if (!words(z, d, zw, k) || !shift_of(shift, k, c, nullptr) || !off_domain(zw, d, c, log_rows, k, zn, cn))
-        return NTT_ERR_ARG;
-      const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows;
-      if (overlaps(mat, n * width * eb, values, (size_t)width * d * eb) || overlaps(inv, n * d * eb, values, (size_t)width * d * eb))
-        return NTT_ERR_ARG;
-      DeepArgs<E> A = base_args(log_rows, width, k);
-      A.mat_elems = n * width;
-      A.inv_elems = n * d;
-      A.val_elems = (size_t)width * d;
-      A.vec = aligned16(inv, values);
-      A.strip_log = DeepShape::strip_log(width, MEMW);
-      A.chunk_rows = DeepShape::open_chunk_rows(width, log_rows, MEMW);
-      A.chunks = DeepShape::open_chunks(width, log_rows, MEMW);
-      A.scr_elems = (size_t)A.chunks * (d + 1) * width;
-      {  // K = (z^N - c^N) / (N c^N)
-        V den[1] = {xf::mul(xf::to_work((uint64_t)n % modulus(), k), cn, k)}, di[1];
-        xf::inv<1>(di, den, k);
-        zn[0] = xf::sub(zn[0], cn, k);
-        for (unsigned j = 0; j < 4; ++j) A.k[j] = j < d ? xf::mul(zn[j], di[0], k) : V(0);
-      }
-      for (unsigned j = 0; j < 4; ++j) A.z[j] = zw[j];
-      if (!d_scr.grow(A.scr_elems * eb)) return NTT_ERR_HIP;
-      P.begin(st);
-      hipError_t e = launch_deep_open<E>(d, static_cast<const uint32_t*>(mat), static_cast<const uint32_t*>(inv),
-                                         d_scr.get(), A, st);
-      P.mark(st, "o");
-      if (e == hipSuccess) {
-        e = launch_deep_open_fin<E>(d, d_scr.get(), static_cast<uint32_t*>(values), A, st);
-        P.mark(st, "e");
-      }
-      return Plan::rc_of(e);
+    V zw[4], zn[4], c, cn;
+    if (!X.words(z, d, zw, k) || !X.shift_of(shift, k, c, nullptr) || !off_domain(zw, d, c, log_rows, k, zn, cn))
+      return NTT_ERR_ARG;
+    const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows;
+    if (overlaps(mat, n * width * eb, values, (size_t)width * d * eb) || overlaps(inv, n * d * eb, values, (size_t)width * d * eb))
+      return NTT_ERR_ARG;
+    DeepArgs<E> A = base_args(log_rows, width, k);
+    A.mat_elems = n * width;
+    A.inv_elems = n * d;
+    A.val_elems = (size_t)width * d;
+    A.vec = aligned16(inv, values);
+    A.strip_log = DeepShape::strip_log(width, MEMW);
+    A.chunk_rows = DeepShape::open_chunk_rows(width, log_rows, MEMW);
+    A.chunks = DeepShape::open_chunks(width, log_rows, MEMW);
+    A.scr_elems = (size_t)A.chunks * (d + 1) * width;
+    {  // K = (z^N - c^N) / (N c^N)
+      V den[1] = {xf::mul(xf::to_work((uint64_t)n % X.modulus(), k), cn, k)}, di[1];
+      xf::inv<1>(di, den, k);
+      zn[0] = xf::sub(zn[0], cn, k);
+      for (unsigned j = 0; j < 4; ++j) A.k[j] = j < d ? xf::mul(zn[j], di[0], k) : V(0);
     }
+    for (unsigned j = 0; j < 4; ++j) A.z[j] = zw[j];
+    if (!d_scr.grow(A.scr_elems * eb)) return NTT_ERR_HIP;
+    P.begin(st);
+    hipError_t e = launch_deep_open<E>(d, static_cast<const uint32_t*>(mat), static_cast<const uint32_t*>(inv),
+                                       d_scr.get(), A, st);
+    P.mark(st, "o");
+    if (e == hipSuccess) {
+      e = launch_deep_open_fin<E>(d, d_scr.get(), static_cast<uint32_t*>(values), A, st);
+      P.mark(st, "e");
+    }
+    return Plan::rc_of(e);
   }
 
   int quotient(const void* mat, unsigned width, unsigned log_rows, const void* inv, const void* values, unsigned d,
                uint64_t ext_w, const uint64_t* alpha, const uint64_t* scale, unsigned flags, void* out, hipStream_t st) {
-    if constexpr (!HasMat<E>::value) {
+    deep_k_t<E> k{};
+    if (!mat || !inv || !values || !alpha || !out || (flags & ~NTT_DEEP_ACCUMULATE) || !X.shape_ok(width, log_rows) ||
+        !X.ext_constants(d, ext_w, k))
       return NTT_ERR_ARG;
-    } else {
-      using V = deep_val_t<E>;
-      deep_k_t<E> k{};
-      if (!mat || !inv || !values || !alpha || !out || (flags & ~NTT_DEEP_ACCUMULATE) || !shape_ok(width, log_rows) ||
-          !common(log_rows, d, ext_w, k))
-        return NTT_ERR_ARG;
-      DeepArgs<E> A = base_args(log_rows, width, k);
-      const uint64_t one[4] = {1, 0, 0, 0};
-      if (!words(alpha, d, A.alpha, k) || !words(scale ? scale : one, d, A.scale, k)) return NTT_ERR_ARG;
-      const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows, ob = n * d * eb;
-      if (overlaps(mat, n * width * eb, out, ob) || overlaps(inv, n * d * eb, out, ob) ||
-          overlaps(values, (size_t)width * d * eb, out, ob))
-        return NTT_ERR_ARG;
-      A.mat_elems = n * width;
-      A.inv_elems = A.out_elems = n * d;
-      A.val_elems = (size_t)width * d;
-      A.vec = aligned16(inv, values, out);
-      A.flags = flags;
-      A.lanes_log = DeepShape::lanes_log(width, MEMW);
-      A.scr_elems = DeepShape::SCR_TAB + (size_t)width * d;
-      if (!d_scr.grow(A.scr_elems * eb)) return NTT_ERR_HIP;
-      P.begin(st);
-      hipError_t e = launch_deep_qpro<E>(d, static_cast<const uint32_t*>(values), d_scr.get(), A, st);
-      P.mark(st, "a");
-      if (e == hipSuccess) {
-        e = launch_deep_quotient<E>(d, static_cast<const uint32_t*>(mat), static_cast<const uint32_t*>(inv), d_scr.get(),
-                                    static_cast<uint32_t*>(out), A, st);
-        P.mark(st, "q");
-      }
-      return Plan::rc_of(e);
+    DeepArgs<E> A = base_args(log_rows, width, k);
+    const uint64_t one[4] = {1, 0, 0, 0};
+    if (!X.words(alpha, d, A.alpha, k) || !X.words(scale ? scale : one, d, A.scale, k)) return NTT_ERR_ARG;
+    const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows, ob = n * d * eb;
+    if (overlaps(mat, n * width * eb, out, ob) || overlaps(inv, n * d * eb, out, ob) ||
+        overlaps(values, (size_t)width * d * eb, out, ob))
+      return NTT_ERR_ARG;
+    A.mat_elems = n * width;
+    A.inv_elems = A.out_elems = n * d;
+    A.val_elems = (size_t)width * d;
+    A.vec = aligned16(inv, values, out);
+    A.flags = flags;
+    A.lanes_log = DeepShape::lanes_log(width, MEMW);
+    A.scr_elems = DeepShape::SCR_TAB + (size_t)width * d;
+    if (!d_scr.grow(A.scr_elems * eb)) return NTT_ERR_HIP;
+    P.begin(st);
+    hipError_t e = launch_deep_qpro<E>(d, static_cast<const uint32_t*>(values), d_scr.get(), A, st);
+    P.mark(st, "a");
+    if (e == hipSuccess) {
+      e = launch_deep_quotient<E>(d, static_cast<const uint32_t*>(mat), static_cast<const uint32_t*>(inv), d_scr.get(),
+                                  static_cast<uint32_t*>(out), A, st);
+      P.mark(st, "q");
     }
+    return Plan::rc_of(e);
   }
 
+  // the shape alone: a twiddle-only plan answers too
   int info(unsigned width, unsigned log_rows, unsigned d, unsigned* open_row_chunks, unsigned* quotient_lanes_per_row) const {
-    if constexpr (!HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!open_row_chunks || !quotient_lanes_per_row || !shape_ok(width, log_rows) || log_rows > P.log_n ||
-          (d != 1 && d != 2 && d != 4))
-        return NTT_ERR_ARG;
-      *open_row_chunks = DeepShape::open_chunks(width, log_rows, MEMW);
-      *quotient_lanes_per_row = 1u << DeepShape::lanes_log(width, MEMW);
-      return NTT_OK;
-    }
-  }
-
-  uint64_t modulus() const {
-    if constexpr (std::is_same_v<E, Eng31>) return P.H.M.p[0];
-    else return kGoldilocksP;
+    if (!open_row_chunks || !quotient_lanes_per_row || !X.shape_ok(width, log_rows) || !degree_ok(d)) return NTT_ERR_ARG;
+    *open_row_chunks = DeepShape::open_chunks(width, log_rows, MEMW);
+    *quotient_lanes_per_row = 1u << DeepShape::lanes_log(width, MEMW);
+    return NTT_OK;
   }
 };
 

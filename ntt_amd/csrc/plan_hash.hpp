@@ -4,54 +4,29 @@
 // pairs on the 4-byte fields -- into the one buffer the calls own: Layout<T>::MAX_ELEMS elements, allocated at
 // the first set, whatever N.  The launching calls check their arguments, then enqueue: a commit is one leaf
 // launch, one launch per layer down to 2^tail_log nodes, and one workgroup for the last tail_log layers.
-// A plan owns one Hash and hands it a reference to itself.  Included by ntt_plan.cpp alone.
+// A Prover (plan_prover.hpp) owns one Hash and hands it a reference to itself: X, whose checks and field
+// constants the calls share with the other features, and through it the plan P.  Included by plan_prover.hpp alone.
 #pragma once
+#include <utility>
 #include <vector>
-
-#include "ntt_kernels.hpp"
-#include "plan_devmem.hpp"
-#include "plan_schedule.hpp"
 
 namespace {
 
 template <class E, class Plan>
 struct Hash {
   static constexpr int MEMW = E::MEMW;
-  static constexpr unsigned T = ntt::MerkleShape::width_t(E::MEMW), D = T / 2;
-  using V = ntt::deep_val_t<E>;
+  static constexpr unsigned T = MerkleShape::width_t(E::MEMW), D = T / 2;
+  using V = deep_val_t<E>;
+  Prover<E, Plan>& X;
   Plan& P;
   DevBuf d_tab;  // the constant table (poseidon2.hpp Layout<T>)
   bool ready = false;
   unsigned alpha = 0, rounds_f = 0, rounds_p = 0;
-  explicit Hash(Plan& plan) : P(plan) {}
+  explicit Hash(Prover<E, Plan>& prover) : X(prover), P(prover.P) {}
 
-  uint64_t modulus() const {
-    if constexpr (std::is_same_v<E, ntt::Eng31>) return P.H.M.p[0];
-    else return ntt::gl64::kP;
-  }
-  ntt::hash_k_t<E> constants() const {
-    ntt::hash_k_t<E> k{};
-    if constexpr (std::is_same_v<E, ntt::Eng31>) {
-      const uint64_t p = P.H.M.p[0], r = (1ull << 32) % p;
-      k.p = (uint32_t)p;
-      k.pinv = ntt::f31::pinv32(k.p);
-      k.one = (uint32_t)r;
-      k.r2 = (uint32_t)(r * r % p);
-      k.mont = (P.flags & NTT_PLAN_MONTGOMERY_IO) ? 1u : 0u;
-    } else {
-      k.one = 1;
-    }
-    return k;
-  }
-  bool usable() const { return !(P.flags & NTT_PLAN_TWIDDLE_ONLY); }
-  // width and N width < 2^32, log_rows within the plan
-  bool shape_ok(unsigned width, unsigned log_rows) const {
-    return width != 0 && log_rows <= P.log_n && log_rows < 32 && ((uint64_t)width << log_rows) < (1ull << 32);
-  }
-  static bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
-  ntt::HashArgs<E> base_args() const {
-    ntt::HashArgs<E> A{};
-    A.K = constants();
+  HashArgs<E> base_args() const {
+    HashArgs<E> A{};
+    A.K = X.constants();
     A.dbg = P.Ff.dbg;
     A.rounds_f = rounds_f;
     A.rounds_p = rounds_p;
@@ -60,121 +35,101 @@ struct Hash {
 
   int set(unsigned width, unsigned sbox_degree, unsigned rf, unsigned rp, const uint64_t* ext_rc, const uint64_t* int_rc,
           const uint64_t* int_diag) {
-    if constexpr (!ntt::HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!usable() || width != T || !ext_rc || !int_diag || (rp && !int_rc)) return NTT_ERR_ARG;
-      if (!ntt::p2::shape_ok(modulus(), sbox_degree, rf, rp)) return NTT_ERR_ARG;
-      std::vector<V> host(ntt::p2::Layout<T>::MAX_ELEMS, V(0));
-      if (!ntt::p2::pack<T>(host.data(), modulus(), rf, rp, ext_rc, int_rc, int_diag, constants())) return NTT_ERR_ARG;
-      if (!d_tab && !d_tab.alloc(host.size() * sizeof(V))) return NTT_ERR_HIP;
-      if (hipMemcpy(d_tab.get(), host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice) != hipSuccess) return NTT_ERR_HIP;
-      alpha = sbox_degree, rounds_f = rf, rounds_p = rp;
-      ready = true;
-      return NTT_OK;
-    }
+    if (!X.usable() || width != T || !ext_rc || !int_diag || (rp && !int_rc)) return NTT_ERR_ARG;
+    if (!p2::shape_ok(X.modulus(), sbox_degree, rf, rp)) return NTT_ERR_ARG;
+    std::vector<V> host(p2::Layout<T>::MAX_ELEMS, V(0));
+    if (!p2::pack<T>(host.data(), X.modulus(), rf, rp, ext_rc, int_rc, int_diag, X.constants())) return NTT_ERR_ARG;
+    if (!d_tab && !d_tab.alloc(host.size() * sizeof(V))) return NTT_ERR_HIP;
+    if (hipMemcpy(d_tab.get(), host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice) != hipSuccess) return NTT_ERR_HIP;
+    alpha = sbox_degree, rounds_f = rf, rounds_p = rp;
+    ready = true;
+    return NTT_OK;
   }
 
   int permute(void* states, uint64_t count, hipStream_t st) {
-    if constexpr (!ntt::HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!usable() || !ready || !states || count == 0 || count > (1ull << 32)) return NTT_ERR_ARG;
-      ntt::HashArgs<E> A = base_args();
-      A.count = count;
-      A.st_elems = (size_t)count * T;
-      A.vec = aligned16(states);
-      P.begin(st);
-      const hipError_t e = ntt::launch_p2_permute<E>(alpha, static_cast<uint32_t*>(states), d_tab.template get<V>(), A, st);
-      P.mark(st, "p");
-      return Plan::rc_of(e);
-    }
+    if (!X.usable() || !ready || !states || count == 0 || count > (1ull << 32)) return NTT_ERR_ARG;
+    HashArgs<E> A = base_args();
+    A.count = count;
+    A.st_elems = (size_t)count * T;
+    A.vec = aligned16(states);
+    P.begin(st);
+    const hipError_t e = launch_p2_permute<E>(alpha, static_cast<uint32_t*>(states), d_tab.template get<V>(), A, st);
+    P.mark(st, "p");
+    return Plan::rc_of(e);
   }
 
   int commit(const void* mat, unsigned width, unsigned log_rows, void* tree, hipStream_t st) {
-    if constexpr (!ntt::HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!usable() || !ready || !mat || !tree || !shape_ok(width, log_rows)) return NTT_ERR_ARG;
-      const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows;
-      if (overlaps(mat, n * width * eb, tree, (2 * n - 1) * D * eb)) return NTT_ERR_ARG;
-      ntt::HashArgs<E> A = base_args();
-      A.log_rows = log_rows;
-      A.width = width;
-      A.mat_elems = n * width;
-      A.tree_elems = (2 * n - 1) * D;
-      A.vec = aligned16(mat) && ((size_t)width * eb) % 16 == 0;
-      A.vec_tree = aligned16(tree);
-      uint32_t* t = static_cast<uint32_t*>(tree);
-      const V* tab = d_tab.template get<V>();
-      P.begin(st);
-      hipError_t e = ntt::launch_merkle_leaf<E>(alpha, static_cast<const uint32_t*>(mat), t, tab, A, st);
-      P.mark(st, "h");
-      const unsigned tail = ntt::MerkleShape::tail_log(log_rows);
-      for (unsigned l = 1; e == hipSuccess && l + tail <= log_rows; ++l) {  // layers of more than 2^tail nodes' children
-        A.in_node = ntt::MerkleShape::layer_start(log_rows, l - 1);
-        A.out_node = ntt::MerkleShape::layer_start(log_rows, l);
-        A.count = n >> l;
-        e = ntt::launch_merkle_layer<E>(alpha, t, tab, A, st);
-        P.mark(st, "m", 1);
-      }
-      if (e == hipSuccess && tail) {
-        A.in_node = ntt::MerkleShape::layer_start(log_rows, log_rows - tail);
-        A.layers = tail;
-        e = ntt::launch_merkle_tail<E>(alpha, t, tab, A, st);
-        P.mark(st, "m", tail);
-      }
-      return Plan::rc_of(e);
+    if (!X.usable() || !ready || !mat || !tree || !X.shape_ok(width, log_rows)) return NTT_ERR_ARG;
+    const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows;
+    if (overlaps(mat, n * width * eb, tree, (2 * n - 1) * D * eb)) return NTT_ERR_ARG;
+    HashArgs<E> A = base_args();
+    A.log_rows = log_rows;
+    A.width = width;
+    A.mat_elems = n * width;
+    A.tree_elems = (2 * n - 1) * D;
+    A.vec = aligned16(mat) && ((size_t)width * eb) % 16 == 0;
+    A.vec_tree = aligned16(tree);
+    uint32_t* t = static_cast<uint32_t*>(tree);
+    const V* tab = d_tab.template get<V>();
+    P.begin(st);
+    hipError_t e = launch_merkle_leaf<E>(alpha, static_cast<const uint32_t*>(mat), t, tab, A, st);
+    P.mark(st, "h");
+    const unsigned tail = MerkleShape::tail_log(log_rows);
+    for (unsigned l = 1; e == hipSuccess && l + tail <= log_rows; ++l) {  // layers of more than 2^tail nodes' children
+      A.in_node = MerkleShape::layer_start(log_rows, l - 1);
+      A.out_node = MerkleShape::layer_start(log_rows, l);
+      A.count = n >> l;
+      e = launch_merkle_layer<E>(alpha, t, tab, A, st);
+      P.mark(st, "m", 1);
     }
+    if (e == hipSuccess && tail) {
+      A.in_node = MerkleShape::layer_start(log_rows, log_rows - tail);
+      A.layers = tail;
+      e = launch_merkle_tail<E>(alpha, t, tab, A, st);
+      P.mark(st, "m", tail);
+    }
+    return Plan::rc_of(e);
   }
 
   int open(const void* mat, unsigned width, unsigned log_rows, const void* tree, const uint32_t* index, unsigned nq,
            void* rows, void* paths, hipStream_t st) {
-    if constexpr (!ntt::HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!usable() || !ready || !tree || !index || nq == 0 || !shape_ok(width, log_rows)) return NTT_ERR_ARG;
-      if ((mat == nullptr) != (rows == nullptr)) return NTT_ERR_ARG;
-      if (!paths && log_rows) return NTT_ERR_ARG;  // a tree of one node has no path
-      const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows;
-      const size_t mat_b = mat ? n * width * eb : 0, tree_b = (2 * n - 1) * D * eb, idx_b = (size_t)nq * 4;
-      const size_t rows_b = rows ? (size_t)nq * width * eb : 0, paths_b = (size_t)nq * log_rows * D * eb;
-      for (const auto& o : {std::pair<const void*, size_t>{rows, rows_b}, {paths, paths_b}}) {
-        if (!o.first || !o.second) continue;
-        if ((mat && overlaps(mat, mat_b, o.first, o.second)) || overlaps(tree, tree_b, o.first, o.second) ||
-            overlaps(index, idx_b, o.first, o.second))
-          return NTT_ERR_ARG;
-      }
-      ntt::HashArgs<E> A = base_args();
-      A.log_rows = log_rows;
-      A.width = width;
-      A.nq = nq;
-      A.mat_elems = n * width;
-      A.tree_elems = (2 * n - 1) * D;
-      A.idx_elems = nq;
-      A.rows_elems = (size_t)nq * width;
-      A.paths_elems = (size_t)nq * log_rows * D;
-      P.begin(st);
-      const hipError_t e = ntt::launch_merkle_open<E>(static_cast<const uint32_t*>(mat), static_cast<const uint32_t*>(tree), index,
-                                                      static_cast<uint32_t*>(rows), static_cast<uint32_t*>(paths), A, st);
-      P.mark(st, "g");
-      return Plan::rc_of(e);
+    if (!X.usable() || !ready || !tree || !index || nq == 0 || !X.shape_ok(width, log_rows)) return NTT_ERR_ARG;
+    if ((mat == nullptr) != (rows == nullptr)) return NTT_ERR_ARG;
+    if (!paths && log_rows) return NTT_ERR_ARG;  // a tree of one node has no path
+    const size_t eb = (size_t)MEMW * 4, n = (size_t)1 << log_rows;
+    const size_t mat_b = mat ? n * width * eb : 0, tree_b = (2 * n - 1) * D * eb, idx_b = (size_t)nq * 4;
+    const size_t rows_b = rows ? (size_t)nq * width * eb : 0, paths_b = (size_t)nq * log_rows * D * eb;
+    for (const auto& o : {std::pair<const void*, size_t>{rows, rows_b}, {paths, paths_b}}) {
+      if (!o.first || !o.second) continue;
+      if ((mat && overlaps(mat, mat_b, o.first, o.second)) || overlaps(tree, tree_b, o.first, o.second) ||
+          overlaps(index, idx_b, o.first, o.second))
+        return NTT_ERR_ARG;
     }
+    HashArgs<E> A = base_args();
+    A.log_rows = log_rows;
+    A.width = width;
+    A.nq = nq;
+    A.mat_elems = n * width;
+    A.tree_elems = (2 * n - 1) * D;
+    A.idx_elems = nq;
+    A.rows_elems = (size_t)nq * width;
+    A.paths_elems = (size_t)nq * log_rows * D;
+    P.begin(st);
+    const hipError_t e = launch_merkle_open<E>(static_cast<const uint32_t*>(mat), static_cast<const uint32_t*>(tree), index,
+                                               static_cast<uint32_t*>(rows), static_cast<uint32_t*>(paths), A, st);
+    P.mark(st, "g");
+    return Plan::rc_of(e);
   }
 
   // the shape alone: needs no parameters
   int info(unsigned width, unsigned log_rows, unsigned* digest_elems, uint64_t* tree_elems, unsigned* launches,
            unsigned* tail_log) const {
-    if constexpr (!ntt::HasMat<E>::value) {
-      return NTT_ERR_ARG;
-    } else {
-      if (!usable() || !digest_elems || !tree_elems || !launches || !tail_log || !shape_ok(width, log_rows)) return NTT_ERR_ARG;
-      *digest_elems = D;
-      *tree_elems = ((2ull << log_rows) - 1) * D;
-      *launches = ntt::MerkleShape::launches(log_rows);
-      *tail_log = ntt::MerkleShape::tail_log(log_rows);
-      return NTT_OK;
-    }
+    if (!X.usable() || !digest_elems || !tree_elems || !launches || !tail_log || !X.shape_ok(width, log_rows)) return NTT_ERR_ARG;
+    *digest_elems = D;
+    *tree_elems = ((2ull << log_rows) - 1) * D;
+    *launches = MerkleShape::launches(log_rows);
+    *tail_log = MerkleShape::tail_log(log_rows);
+    return NTT_OK;
   }
 };
 

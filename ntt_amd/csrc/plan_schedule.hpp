@@ -210,4 +210,16 @@ static bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_byte
   return a0 < b1 && b0 < a1;
 }
 
+// The checks of the prover-stage calls (plan_prover.hpp) that need no plan.
+// An element is one of F_p (d = 1) or of F_p[X]/(X^d - W), d = 2 or 4
+static bool degree_ok(unsigned d) { return d == 1 || d == 2 || d == 4; }
+// Every pointer given (null: none) is 16-byte aligned: the kernels may then use 16-byte accesses
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+// A [2^log_rows][width] matrix is not empty and every index of an element of it fits 32 bits
+static bool fits32(unsigned width, unsigned log_rows) {
+  return width != 0 && log_rows < 32 && ((uint64_t)width << log_rows) < (1ull << 32);
+}
+
 }  // namespace

@@ -37,6 +37,14 @@ def _u64_array(values: Sequence[int]):
     return arr
 
 
+def _ptr(t: torch.Tensor) -> C.c_void_p:
+    return C.c_void_p(t.data_ptr())
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
 def int_to_limbs(v: int, limbs64: int) -> List[int]:
     return [(v >> (64 * i)) & ((1 << 64) - 1) for i in range(limbs64)]
 
@@ -164,27 +172,102 @@ class NTTPlan:
         shape = (batch * self.n,) if self.limbs64 == 1 else (batch * self.n, self.limbs64)
         return torch.empty(shape, dtype=self.dtype, device=f"cuda:{self.device}")
 
-    def _check_tensor(self, t: torch.Tensor, batch: int = 1) -> None:
+    def _check_tensor(self, t: torch.Tensor, batch: int = 1, what: str = "NTT data", count: Optional[int] = None) -> None:
+        """``t`` holds ``count`` elements (default: ``batch`` vectors of the plan's size) on the plan's device."""
+        count = batch * self.n if count is None else count
         if not t.is_cuda:
-            raise ValueError("NTT data must be a device (HIP) tensor")
-        if not t.is_contiguous() or t.dtype != self.dtype:
-            raise ValueError("NTT data must be a contiguous int64 tensor in the cgbn_mem_t layout"
-                             if not self.elem32 else "NTT data must be a contiguous int32 tensor (4-byte elements)")
-        if t.numel() * t.element_size() != batch * self.n * self.elem_bytes:
-            raise ValueError(f"expected {batch * self.n} elements of {self.elem_bytes} bytes")
+            raise ValueError(f"{what} must be a device (HIP) tensor")
+        self._check_layout(t, what)
+        if t.numel() * t.element_size() != count * self.elem_bytes:
+            raise ValueError(f"{what}: expected {count} elements of {self.elem_bytes} bytes")
         if t.device.index != self.device:
-            raise ValueError(f"tensor on {t.device}, plan on cuda:{self.device}")
+            raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
+
+    # -------------------------------------------------------------------------------- argument checks
+    # Shared by the calls below.  Each raises ValueError; the calls check scalars first, then shapes and overlap,
+    # and whether a tensor is on the plan's device last.
+    def _check_layout(self, t, what: str) -> None:
+        if not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.dtype != self.dtype:
+            raise ValueError(f"{what} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the plan's "
+                             "element layout")
+
+    def _check_device(self, *named) -> None:
+        """``named`` = (tensor or None, name) pairs: every tensor is on the plan's device."""
+        for t, what in named:
+            if t is None:
+                continue
+            if not t.is_cuda:
+                raise ValueError(f"{what} must be a device (HIP) tensor")
+            if t.device.index != self.device:
+                raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
+
+    def _check_log_rows(self, log_rows, lowest=0, lowest_name: str = "0") -> int:
+        """``log_rows`` (None: the plan's log_n) is an integer in [lowest, log_n].  Returns it."""
+        if log_rows is None:
+            log_rows = self.log_n
+        if not _is_int(log_rows) or not lowest <= log_rows <= self.log_n:
+            raise ValueError(f"log_rows must be an integer in [{lowest_name}, {self.log_n}], not {log_rows!r}")
+        return log_rows
+
+    def _check_shape(self, width, log_rows: int) -> None:
+        """A positive integer width with every element index of [2^log_rows][width] below 2^32."""
+        if not _is_int(width) or width < 1:
+            raise ValueError(f"width must be a positive integer, not {width!r}")
+        if (width << log_rows) >= 1 << 32:
+            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+
+    def _check_matrix(self, t: torch.Tensor, rows: int, width: int, what: str, log_bound: Optional[int] = None) -> None:
+        """``t`` = [rows][width] in the plan's layout; the width is bounded at 2^log_bound rows (None: the plan's n)."""
+        self._check_shape(width, self.log_n if log_bound is None else log_bound)
+        self._check_layout(t, what)
+        if t.numel() * t.element_size() != rows * width * self.elem_bytes:
+            raise ValueError(f"{what}: expected {rows} rows of {width} elements of {self.elem_bytes} bytes")
+
+    def _check_shift(self, shift) -> None:
+        if shift is not None and (not _is_int(shift) or not 0 < shift < self.p):
+            raise ValueError(f"shift must be None or a canonical nonzero integer (0 < shift < p), not {shift!r}")
+
+    def _check_ext(self, ext_degree, ext_w, reads_w: bool = True) -> None:
+        if not _is_int(ext_degree) or ext_degree not in (1, 2, 4):
+            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
+        if reads_w and ext_degree > 1 and (not _is_int(ext_w) or not 0 < ext_w < self.p):
+            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
+
+    def _canonical_words(self, name: str, value, count: int) -> List[int]:
+        """``value`` as a list: a sequence of ``count`` canonical ints."""
+        try:
+            vals = list(value)
+        except TypeError:
+            raise ValueError(f"{name} must be a sequence of {count} integers, not {value!r}") from None
+        if isinstance(value, str) or len(vals) != count or not all(_is_int(v) and 0 <= v < self.p for v in vals):
+            raise ValueError(f"{name} must be {count} canonical integers (0 <= {name}[j] < p), not {value!r}")
+        return vals
+
+    @staticmethod
+    def _check_no_overlap(out, out_name, out_bytes, inputs, same_ok: bool = False) -> None:
+        """``out`` shares no byte with any of ``inputs`` = ((tensor, name, bytes), ..); ``same_ok``: unless it is
+        the same buffer."""
+        b0 = out.data_ptr()
+        for t, name, nbytes in inputs:
+            a0 = t.data_ptr()
+            if a0 < b0 + out_bytes and b0 < a0 + nbytes and not (same_ok and a0 == b0):
+                raise ValueError(f"{name} and {out_name} overlap"
+                                 + (" (they may be the same buffer, or apart)" if same_ok else ""))
+
+    def _shift_arg(self, shift: Optional[int], limbs64: Optional[int] = None):
+        """The ``shift`` pointer of a C call: null, or the shift as ``limbs64`` words (None: the plan's)."""
+        return None if shift is None else _u64_array(int_to_limbs(int(shift), self.limbs64 if limbs64 is None else limbs64))
 
     # -------------------------------------------------------------------------------- transforms
     def forward(self, t: torch.Tensor, stream=None) -> torch.Tensor:
         self._check_tensor(t)
-        _L.check(self._lib.ntt_forward(self._h, C.c_void_p(t.data_ptr()), _stream_ptr(stream, t.device)),
+        _L.check(self._lib.ntt_forward(self._h, _ptr(t), _stream_ptr(stream, t.device)),
                  "ntt_forward")
         return t
 
     def inverse(self, t: torch.Tensor, stream=None) -> torch.Tensor:
         self._check_tensor(t)
-        _L.check(self._lib.ntt_inverse(self._h, C.c_void_p(t.data_ptr()), _stream_ptr(stream, t.device)),
+        _L.check(self._lib.ntt_inverse(self._h, _ptr(t), _stream_ptr(stream, t.device)),
                  "ntt_inverse")
         return t
 
@@ -208,19 +291,19 @@ class NTTPlan:
             raise ValueError("expected a contiguous device tensor in the plan's element layout")
         count = t.numel() if self.limbs64 == 1 else t.numel() // self.limbs64
         bad = C.c_uint64()
-        _L.check(self._lib.ntt_count_noncanonical(self._h, C.c_void_p(t.data_ptr()), count, C.byref(bad),
+        _L.check(self._lib.ntt_count_noncanonical(self._h, _ptr(t), count, C.byref(bad),
                                                   _stream_ptr(stream, t.device)), "ntt_count_noncanonical")
         return bad.value
 
     def forward_batch(self, t: torch.Tensor, batch: int, stream=None) -> torch.Tensor:
         self._check_tensor(t, batch)
-        _L.check(self._lib.ntt_forward_batch(self._h, C.c_void_p(t.data_ptr()), int(batch),
+        _L.check(self._lib.ntt_forward_batch(self._h, _ptr(t), int(batch),
                                              _stream_ptr(stream, t.device)), "ntt_forward_batch")
         return t
 
     def inverse_batch(self, t: torch.Tensor, batch: int, stream=None) -> torch.Tensor:
         self._check_tensor(t, batch)
-        _L.check(self._lib.ntt_inverse_batch(self._h, C.c_void_p(t.data_ptr()), int(batch),
+        _L.check(self._lib.ntt_inverse_batch(self._h, _ptr(t), int(batch),
                                              _stream_ptr(stream, t.device)), "ntt_inverse_batch")
         return t
 
@@ -228,7 +311,7 @@ class NTTPlan:
         """Evaluations on the coset shift*<w>: X_k = sum_j x_j (shift w^k)^j, one vector of the plan's
         size in place (no padding, no batch: ``lde_batch`` is the low-degree extension)."""
         self._check_tensor(t)
-        _L.check(self._lib.ntt_forward_coset(self._h, C.c_void_p(t.data_ptr()),
+        _L.check(self._lib.ntt_forward_coset(self._h, _ptr(t),
                                              _u64_array(int_to_limbs(int(shift), self.limbs64)),
                                              _stream_ptr(stream, t.device)), "ntt_forward_coset")
         return t
@@ -236,7 +319,7 @@ class NTTPlan:
     def inverse_coset(self, t: torch.Tensor, shift: int, stream=None) -> torch.Tensor:
         """Interpolation from the coset shift*<w>: x_j = shift^-j INTT(X)_j."""
         self._check_tensor(t)
-        _L.check(self._lib.ntt_inverse_coset(self._h, C.c_void_p(t.data_ptr()),
+        _L.check(self._lib.ntt_inverse_coset(self._h, _ptr(t),
                                              _u64_array(int_to_limbs(int(shift), self.limbs64)),
                                              _stream_ptr(stream, t.device)), "ntt_inverse_coset")
         return t
@@ -250,19 +333,10 @@ class NTTPlan:
         if shift is not None and not 0 < int(shift) < self.p:
             raise ValueError("shift must be canonical and nonzero (0 < shift < p)")
         n_in = self.n >> log_blowup
-        for t, count, what in ((coeffs, batch * n_in, "coeffs"), (out, batch * self.n, "out")):
-            if not t.is_cuda:
-                raise ValueError(f"{what} must be a device (HIP) tensor")
-            if not t.is_contiguous() or t.dtype != self.dtype:
-                raise ValueError(f"{what} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the "
-                                 "plan's element layout")
-            if t.numel() * t.element_size() != count * self.elem_bytes:
-                raise ValueError(f"{what}: expected {count} elements of {self.elem_bytes} bytes")
-            if t.device.index != self.device:
-                raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
-        a0, b0 = coeffs.data_ptr(), out.data_ptr()
-        if a0 < b0 + batch * self.n * self.elem_bytes and b0 < a0 + batch * n_in * self.elem_bytes:
-            raise ValueError("coeffs and out overlap")
+        self._check_tensor(coeffs, what="coeffs", count=batch * n_in)
+        self._check_tensor(out, what="out", count=batch * self.n)
+        self._check_no_overlap(out, "out", batch * self.n * self.elem_bytes,
+                               ((coeffs, "coeffs", batch * n_in * self.elem_bytes),))
 
     def lde_batch(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int] = None,
                   batch: int = 1, stream=None) -> torch.Tensor:
@@ -271,34 +345,14 @@ class NTTPlan:
         ``batch`` vectors of N evaluations: out[v][k] = sum_j coeffs[v][j] (shift w_N^k)^j (shift None: 1).
         ``coeffs`` is not modified and must not overlap ``out``."""
         self._check_lde(coeffs, out, log_blowup, shift, batch)
-        sh = None if shift is None else _u64_array(int_to_limbs(int(shift), self.limbs64))
-        _L.check(self._lib.ntt_lde_batch(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
-                                         int(log_blowup), sh, int(batch), _stream_ptr(stream, out.device)),
-                 "ntt_lde_batch")
+        _L.check(self._lib.ntt_lde_batch(self._h, _ptr(coeffs), _ptr(out), int(log_blowup), self._shift_arg(shift),
+                                         int(batch), _stream_ptr(stream, out.device)), "ntt_lde_batch")
         return out
 
     # -------------------------------------------------------------------------------- row-major matrices
-    def _check_matrix(self, t: torch.Tensor, rows: int, width: int, what: str) -> None:
-        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
-            raise ValueError(f"width must be a positive integer, not {width!r}")
-        if self.n * width >= 1 << 32:
-            raise ValueError(f"2^log_n * width must stay below 2^32, not {self.n} * {width}")
-        if not t.is_contiguous() or t.dtype != self.dtype:
-            raise ValueError(f"{what} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the "
-                             "plan's element layout")
-        if t.numel() * t.element_size() != rows * width * self.elem_bytes:
-            raise ValueError(f"{what}: expected {rows} rows of {width} elements of {self.elem_bytes} bytes")
-
-    def _check_matrix_device(self, t: torch.Tensor, what: str) -> None:
-        if not t.is_cuda:
-            raise ValueError(f"{what} must be a device (HIP) tensor")
-        if t.device.index != self.device:
-            raise ValueError(f"{what} on {t.device}, plan on cuda:{self.device}")
-
     def _check_matrix_ex(self, shift, flag, flag_name: str) -> None:
         """The keyword options of the matrix calls: a canonical nonzero integer shift (or None), a bool flag."""
-        if shift is not None and (not isinstance(shift, int) or isinstance(shift, bool) or not 0 < shift < self.p):
-            raise ValueError(f"shift must be None or a canonical nonzero integer (0 < shift < p), not {shift!r}")
+        self._check_shift(shift)
         if not isinstance(flag, bool):
             raise ValueError(f"{flag_name} must be a bool, not {flag!r}")
 
@@ -310,13 +364,12 @@ class NTTPlan:
         result at row bitrev(k) (ntt_forward_matrix_ex)."""
         self._check_matrix_ex(shift, bitrev_out, "bitrev_out")
         self._check_matrix(t, self.n, width, "t")
-        self._check_matrix_device(t, "t")
+        self._check_device((t, "t"))
         if shift is None and not bitrev_out:
-            _L.check(self._lib.ntt_forward_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
+            _L.check(self._lib.ntt_forward_matrix(self._h, _ptr(t), int(width),
                                                   _stream_ptr(stream, t.device)), "ntt_forward_matrix")
             return t
-        sh = None if shift is None else _u64_array(int_to_limbs(shift, self.limbs64))
-        _L.check(self._lib.ntt_forward_matrix_ex(self._h, C.c_void_p(t.data_ptr()), int(width), sh,
+        _L.check(self._lib.ntt_forward_matrix_ex(self._h, _ptr(t), int(width), self._shift_arg(shift),
                                                  _L.NTT_MATRIX_BITREV_OUT if bitrev_out else 0,
                                                  _stream_ptr(stream, t.device)), "ntt_forward_matrix_ex")
         return t
@@ -328,13 +381,12 @@ class NTTPlan:
         row i of ``t`` holds the evaluation of natural index bitrev(i) (ntt_inverse_matrix_ex)."""
         self._check_matrix_ex(shift, bitrev_in, "bitrev_in")
         self._check_matrix(t, self.n, width, "t")
-        self._check_matrix_device(t, "t")
+        self._check_device((t, "t"))
         if shift is None and not bitrev_in:
-            _L.check(self._lib.ntt_inverse_matrix(self._h, C.c_void_p(t.data_ptr()), int(width),
+            _L.check(self._lib.ntt_inverse_matrix(self._h, _ptr(t), int(width),
                                                   _stream_ptr(stream, t.device)), "ntt_inverse_matrix")
             return t
-        sh = None if shift is None else _u64_array(int_to_limbs(shift, self.limbs64))
-        _L.check(self._lib.ntt_inverse_matrix_ex(self._h, C.c_void_p(t.data_ptr()), int(width), sh,
+        _L.check(self._lib.ntt_inverse_matrix_ex(self._h, _ptr(t), int(width), self._shift_arg(shift),
                                                  _L.NTT_MATRIX_BITREV_IN if bitrev_in else 0,
                                                  _stream_ptr(stream, t.device)), "ntt_inverse_matrix_ex")
         return t
@@ -348,11 +400,9 @@ class NTTPlan:
         n_in = self.n >> log_blowup
         self._check_matrix(coeffs, n_in, width, "coeffs")
         self._check_matrix(out, self.n, width, "out")
-        a0, b0 = coeffs.data_ptr(), out.data_ptr()
-        if a0 < b0 + self.n * width * self.elem_bytes and b0 < a0 + n_in * width * self.elem_bytes:
-            raise ValueError("coeffs and out overlap")
-        self._check_matrix_device(coeffs, "coeffs")
-        self._check_matrix_device(out, "out")
+        self._check_no_overlap(out, "out", self.n * width * self.elem_bytes,
+                               ((coeffs, "coeffs", n_in * width * self.elem_bytes),))
+        self._check_device((coeffs, "coeffs"), (out, "out"))
 
     def lde_matrix(self, coeffs: torch.Tensor, out: torch.Tensor, log_blowup: int, shift: Optional[int] = None,
                    width: int = 1, stream=None, *, bitrev_out: bool = False) -> torch.Tensor:
@@ -364,15 +414,13 @@ class NTTPlan:
         if not isinstance(bitrev_out, bool):
             raise ValueError(f"bitrev_out must be a bool, not {bitrev_out!r}")
         self._check_lde_matrix(coeffs, out, log_blowup, shift, width)
-        sh = None if shift is None else _u64_array(int_to_limbs(int(shift), self.limbs64))
         if bitrev_out:
-            _L.check(self._lib.ntt_lde_matrix_ex(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                 int(log_blowup), sh, int(width), _L.NTT_MATRIX_BITREV_OUT,
+            _L.check(self._lib.ntt_lde_matrix_ex(self._h, _ptr(coeffs), _ptr(out), int(log_blowup),
+                                                 self._shift_arg(shift), int(width), _L.NTT_MATRIX_BITREV_OUT,
                                                  _stream_ptr(stream, out.device)), "ntt_lde_matrix_ex")
             return out
-        _L.check(self._lib.ntt_lde_matrix(self._h, C.c_void_p(coeffs.data_ptr()), C.c_void_p(out.data_ptr()),
-                                          int(log_blowup), sh, int(width), _stream_ptr(stream, out.device)),
-                 "ntt_lde_matrix")
+        _L.check(self._lib.ntt_lde_matrix(self._h, _ptr(coeffs), _ptr(out), int(log_blowup), self._shift_arg(shift),
+                                          int(width), _stream_ptr(stream, out.device)), "ntt_lde_matrix")
         return out
 
     def fri_fold(self, evals: torch.Tensor, out: torch.Tensor, log_arity: int, beta: Sequence[int], *,
@@ -386,37 +434,19 @@ class NTTPlan:
         f(x) = sum_t x^t f_t(x^(2^log_arity)).  ``beta`` is ``ext_degree`` canonical ints; ``log_rows``
         defaults to the plan's log_n and may be smaller (one plan serves every later layer).  ``evals`` is not
         modified and must not overlap ``out``; ``fields.EXTENSIONS`` has the usual (ext_degree, ext_w)."""
-        def is_int(v):
-            return isinstance(v, int) and not isinstance(v, bool)
-        if log_rows is None:
-            log_rows = self.log_n
-        if not is_int(log_arity) or not 1 <= log_arity <= 4:
+        if not _is_int(log_arity) or not 1 <= log_arity <= 4:
             raise ValueError(f"log_arity must be an integer in [1, 4], not {log_arity!r}")
-        if not is_int(log_rows) or not log_arity <= log_rows <= self.log_n:
-            raise ValueError(f"log_rows must be an integer in [log_arity, {self.log_n}], not {log_rows!r}")
-        if not is_int(ext_degree) or ext_degree not in (1, 2, 4):
-            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
-        if ext_degree > 1 and (not is_int(ext_w) or not 0 < ext_w < self.p):
-            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
-        try:
-            beta = list(beta)
-        except TypeError:
-            raise ValueError(f"beta must be a sequence of {ext_degree} integers, not {beta!r}") from None
-        if len(beta) != ext_degree or not all(is_int(b) and 0 <= b < self.p for b in beta):
-            raise ValueError(f"beta must be {ext_degree} canonical integers (0 <= beta[j] < p), not {beta!r}")
-        self._check_matrix_ex(shift, True, "")
-        rows, rows_out = 1 << log_rows, 1 << (log_rows - log_arity)
+        log_rows = self._check_log_rows(log_rows, log_arity, "log_arity")
+        self._check_ext(ext_degree, ext_w)
+        beta = self._canonical_words("beta", beta, ext_degree)
+        self._check_shift(shift)
+        rows, rows_out, eb = 1 << log_rows, 1 << (log_rows - log_arity), self.elem_bytes
         self._check_matrix(evals, rows, ext_degree, "evals")
         self._check_matrix(out, rows_out, ext_degree, "out")
-        a0, b0 = evals.data_ptr(), out.data_ptr()
-        if a0 < b0 + rows_out * ext_degree * self.elem_bytes and b0 < a0 + rows * ext_degree * self.elem_bytes:
-            raise ValueError("evals and out overlap")
-        self._check_matrix_device(evals, "evals")
-        self._check_matrix_device(out, "out")
-        sh = None if shift is None else _u64_array([shift])
-        _L.check(self._lib.ntt_fri_fold(self._h, C.c_void_p(evals.data_ptr()), C.c_void_p(out.data_ptr()),
-                                        int(log_rows), int(log_arity), int(ext_degree),
-                                        int(ext_w) if ext_degree > 1 else 0, _u64_array(beta), sh,
+        self._check_no_overlap(out, "out", rows_out * ext_degree * eb, ((evals, "evals", rows * ext_degree * eb),))
+        self._check_device((evals, "evals"), (out, "out"))
+        _L.check(self._lib.ntt_fri_fold(self._h, _ptr(evals), _ptr(out), int(log_rows), int(log_arity), int(ext_degree),
+                                        int(ext_w) if ext_degree > 1 else 0, _u64_array(beta), self._shift_arg(shift, 1),
                                         _stream_ptr(stream, out.device)), "ntt_fri_fold")
         return out
 
@@ -424,39 +454,17 @@ class NTTPlan:
     def _check_deep(self, ext_degree, ext_w, shift, log_rows, words) -> int:
         """The scalar arguments the DEEP calls share; ``words`` = ((name, value, may_be_none), ..): sequences of
         ``ext_degree`` canonical ints.  Returns log_rows."""
-        def is_int(v):
-            return isinstance(v, int) and not isinstance(v, bool)
-        if log_rows is None:
-            log_rows = self.log_n
-        if not is_int(log_rows) or not 0 <= log_rows <= self.log_n:
-            raise ValueError(f"log_rows must be an integer in [0, {self.log_n}], not {log_rows!r}")
-        if not is_int(ext_degree) or ext_degree not in (1, 2, 4):
-            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
-        if ext_degree > 1 and (not is_int(ext_w) or not 0 < ext_w < self.p):
-            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
+        log_rows = self._check_log_rows(log_rows)
+        self._check_ext(ext_degree, ext_w)
         for name, value, optional in words:
-            if value is None and optional:
-                continue
-            try:
-                vals = list(value)
-            except TypeError:
-                raise ValueError(f"{name} must be a sequence of {ext_degree} integers, not {value!r}") from None
-            if isinstance(value, str) or len(vals) != ext_degree or not all(is_int(v) and 0 <= v < self.p for v in vals):
-                raise ValueError(f"{name} must be {ext_degree} canonical integers (0 <= {name}[j] < p), not {value!r}")
-        self._check_matrix_ex(shift, True, "")
+            if value is not None or not optional:
+                self._canonical_words(name, value, ext_degree)
+        self._check_shift(shift)
         return log_rows
 
     def _check_on_domain(self, z, shift, log_rows) -> None:
         if not any(z[1:]) and pow(z[0], 1 << log_rows, self.p) == pow(1 if shift is None else shift, 1 << log_rows, self.p):
             raise ValueError("z lies on the evaluation domain shift*<w_N>")
-
-    @staticmethod
-    def _check_no_overlap(out, out_name, out_bytes, inputs) -> None:
-        b0 = out.data_ptr()
-        for t, name, nbytes in inputs:
-            a0 = t.data_ptr()
-            if a0 < b0 + out_bytes and b0 < a0 + nbytes:
-                raise ValueError(f"{name} and {out_name} overlap")
 
     def deep_points(self, out: torch.Tensor, z: Sequence[int], *, ext_degree: int = 1, ext_w: int = 0,
                     shift: Optional[int] = None, bitrev: bool = False, log_rows: Optional[int] = None,
@@ -471,10 +479,9 @@ class NTTPlan:
         z = list(z)
         self._check_on_domain(z, shift, log_rows)
         self._check_matrix(out, 1 << log_rows, ext_degree, "out")
-        self._check_matrix_device(out, "out")
-        sh = None if shift is None else _u64_array([shift])
-        _L.check(self._lib.ntt_deep_points(self._h, C.c_void_p(out.data_ptr()), int(log_rows), int(ext_degree),
-                                           int(ext_w) if ext_degree > 1 else 0, _u64_array(z), sh,
+        self._check_device((out, "out"))
+        _L.check(self._lib.ntt_deep_points(self._h, _ptr(out), int(log_rows), int(ext_degree),
+                                           int(ext_w) if ext_degree > 1 else 0, _u64_array(z), self._shift_arg(shift, 1),
                                            _L.NTT_MATRIX_BITREV_OUT if bitrev else 0,
                                            _stream_ptr(stream, out.device)), "ntt_deep_points")
         return out
@@ -491,32 +498,18 @@ class NTTPlan:
         z = list(z)
         self._check_on_domain(z, shift, log_rows)
         rows = 1 << log_rows
-        self._check_deep_matrix(mat, rows, width)
+        self._check_matrix(mat, rows, width, "mat", log_rows)
         self._check_matrix(inv, rows, ext_degree, "inv")
         self._check_matrix(values, width, ext_degree, "values")
         eb = self.elem_bytes
         self._check_no_overlap(values, "values", width * ext_degree * eb,
                                ((mat, "mat", rows * width * eb), (inv, "inv", rows * ext_degree * eb)))
-        for t, what in ((mat, "mat"), (inv, "inv"), (values, "values")):
-            self._check_matrix_device(t, what)
-        sh = None if shift is None else _u64_array([shift])
-        _L.check(self._lib.ntt_matrix_open(self._h, C.c_void_p(mat.data_ptr()), int(width), int(log_rows),
-                                           C.c_void_p(inv.data_ptr()), int(ext_degree),
-                                           int(ext_w) if ext_degree > 1 else 0, _u64_array(z), sh,
-                                           _L.NTT_MATRIX_BITREV_OUT if bitrev else 0, C.c_void_p(values.data_ptr()),
+        self._check_device((mat, "mat"), (inv, "inv"), (values, "values"))
+        _L.check(self._lib.ntt_matrix_open(self._h, _ptr(mat), int(width), int(log_rows), _ptr(inv), int(ext_degree),
+                                           int(ext_w) if ext_degree > 1 else 0, _u64_array(z), self._shift_arg(shift, 1),
+                                           _L.NTT_MATRIX_BITREV_OUT if bitrev else 0, _ptr(values),
                                            _stream_ptr(stream, values.device)), "ntt_matrix_open")
         return values
-
-    def _check_deep_matrix(self, mat: torch.Tensor, rows: int, width) -> None:
-        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
-            raise ValueError(f"width must be a positive integer, not {width!r}")
-        if rows * width >= 1 << 32:
-            raise ValueError(f"2^log_rows * width must stay below 2^32, not {rows} * {width}")
-        if not mat.is_contiguous() or mat.dtype != self.dtype:
-            raise ValueError(f"mat must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the plan's "
-                             "element layout")
-        if mat.numel() * mat.element_size() != rows * width * self.elem_bytes:
-            raise ValueError(f"mat: expected {rows} rows of {width} elements of {self.elem_bytes} bytes")
 
     def deep_quotient(self, mat: torch.Tensor, width: int, inv: torch.Tensor, values: torch.Tensor, out: torch.Tensor,
                       alpha: Sequence[int], *, scale: Optional[Sequence[int]] = None, accumulate: bool = False,
@@ -528,7 +521,7 @@ class NTTPlan:
         if not isinstance(accumulate, bool):
             raise ValueError(f"accumulate must be a bool, not {accumulate!r}")
         rows = 1 << log_rows
-        self._check_deep_matrix(mat, rows, width)
+        self._check_matrix(mat, rows, width, "mat", log_rows)
         self._check_matrix(inv, rows, ext_degree, "inv")
         self._check_matrix(values, width, ext_degree, "values")
         self._check_matrix(out, rows, ext_degree, "out")
@@ -536,13 +529,12 @@ class NTTPlan:
         self._check_no_overlap(out, "out", rows * ext_degree * eb,
                                ((mat, "mat", rows * width * eb), (inv, "inv", rows * ext_degree * eb),
                                 (values, "values", width * ext_degree * eb)))
-        for t, what in ((mat, "mat"), (inv, "inv"), (values, "values"), (out, "out")):
-            self._check_matrix_device(t, what)
-        _L.check(self._lib.ntt_deep_quotient(self._h, C.c_void_p(mat.data_ptr()), int(width), int(log_rows),
-                                             C.c_void_p(inv.data_ptr()), C.c_void_p(values.data_ptr()), int(ext_degree),
+        self._check_device((mat, "mat"), (inv, "inv"), (values, "values"), (out, "out"))
+        _L.check(self._lib.ntt_deep_quotient(self._h, _ptr(mat), int(width), int(log_rows),
+                                             _ptr(inv), _ptr(values), int(ext_degree),
                                              int(ext_w) if ext_degree > 1 else 0, _u64_array(list(alpha)),
                                              None if scale is None else _u64_array(list(scale)),
-                                             _L.NTT_DEEP_ACCUMULATE if accumulate else 0, C.c_void_p(out.data_ptr()),
+                                             _L.NTT_DEEP_ACCUMULATE if accumulate else 0, _ptr(out),
                                              _stream_ptr(stream, out.device)), "ntt_deep_quotient")
         return out
 
@@ -550,10 +542,7 @@ class NTTPlan:
         """(open_row_chunks, quotient_lanes_per_row) of ``open_matrix`` and ``deep_quotient`` at this shape
         (ntt_deep_info)."""
         log_rows = self._check_deep(ext_degree, 1, None, log_rows, ())
-        if not isinstance(width, int) or isinstance(width, bool) or width < 1:
-            raise ValueError(f"width must be a positive integer, not {width!r}")
-        if (width << log_rows) >= 1 << 32:
-            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+        self._check_shape(width, log_rows)
         chunks, lanes = C.c_uint(), C.c_uint()
         _L.check(self._lib.ntt_deep_info(self._h, int(width), int(log_rows), int(ext_degree), C.byref(chunks),
                                          C.byref(lanes)), "ntt_deep_info")
@@ -567,14 +556,12 @@ class NTTPlan:
             return 16
         return 8 if (self.limbs64 == 1 and self.p == FIELDS[3][1]) else 0
 
-    @staticmethod
-    def _is_int(v) -> bool:
-        return isinstance(v, int) and not isinstance(v, bool)
-
-    def _check_hashing(self) -> int:
+    def _check_hashing(self, needs_parameters: bool = False) -> int:
         t = self.poseidon2_width
         if not t:
             raise ValueError("Poseidon2 hashing needs a Goldilocks plan or a plan of 4-byte elements")
+        if needs_parameters and getattr(self, "_poseidon2", None) is None:
+            raise ValueError("set_poseidon2 must be called first")
         return t
 
     def set_poseidon2(self, sbox_degree: int, rounds_f: int, rounds_p: int, ext_rc, int_rc: Sequence[int],
@@ -583,26 +570,17 @@ class NTTPlan:
         coprime to p - 1, ``rounds_f`` even in [2, 16], ``rounds_p`` in [0, 64], ``ext_rc`` = rounds_f rows of t
         canonical ints, ``int_rc`` = rounds_p, ``int_diag`` = t of them.  Blocking; may be called again."""
         t = self._check_hashing()
-        if width is not None and (not self._is_int(width) or width != t):
+        if width is not None and (not _is_int(width) or width != t):
             raise ValueError(f"width must be {t} on this plan, not {width!r}")
-        if not self._is_int(sbox_degree) or sbox_degree not in (3, 5, 7):
+        if not _is_int(sbox_degree) or sbox_degree not in (3, 5, 7):
             raise ValueError(f"sbox_degree must be 3, 5 or 7, not {sbox_degree!r}")
         if (self.p - 1) % sbox_degree == 0:
             raise ValueError(f"sbox_degree {sbox_degree} divides p - 1: x^{sbox_degree} is no permutation of the field")
-        if not self._is_int(rounds_f) or not 2 <= rounds_f <= 16 or rounds_f % 2:
+        if not _is_int(rounds_f) or not 2 <= rounds_f <= 16 or rounds_f % 2:
             raise ValueError(f"rounds_f must be an even integer in [2, 16], not {rounds_f!r}")
-        if not self._is_int(rounds_p) or not 0 <= rounds_p <= 64:
+        if not _is_int(rounds_p) or not 0 <= rounds_p <= 64:
             raise ValueError(f"rounds_p must be an integer in [0, 64], not {rounds_p!r}")
-
-        def words(name, value, count):
-            try:
-                vals = list(value)
-            except TypeError:
-                raise ValueError(f"{name} must be a sequence of {count} integers, not {value!r}") from None
-            if isinstance(value, str) or len(vals) != count or not all(self._is_int(v) and 0 <= v < self.p for v in vals):
-                raise ValueError(f"{name} must be {count} canonical integers (0 <= v < p)")
-            return vals
-
+        words = self._canonical_words
         try:
             ext_rows = list(ext_rc)
         except TypeError:
@@ -619,30 +597,19 @@ class NTTPlan:
 
     def _check_hash_call(self, width, log_rows) -> int:
         """The arguments the Merkle calls share.  Returns log_rows."""
-        self._check_hashing()
-        if getattr(self, "_poseidon2", None) is None:
-            raise ValueError("set_poseidon2 must be called first")
-        if log_rows is None:
-            log_rows = self.log_n
-        if not self._is_int(log_rows) or not 0 <= log_rows <= self.log_n:
-            raise ValueError(f"log_rows must be an integer in [0, {self.log_n}], not {log_rows!r}")
-        if not self._is_int(width) or width < 1:
-            raise ValueError(f"width must be a positive integer, not {width!r}")
-        if (width << log_rows) >= 1 << 32:
-            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+        self._check_hashing(needs_parameters=True)
+        log_rows = self._check_log_rows(log_rows)
+        self._check_shape(width, log_rows)
         return log_rows
 
     def poseidon2_permute(self, states: torch.Tensor, stream=None) -> torch.Tensor:
         """Permute ``states`` = [count][t] in place (ntt_poseidon2_permute)."""
-        t = self._check_hashing()
-        if getattr(self, "_poseidon2", None) is None:
-            raise ValueError("set_poseidon2 must be called first")
-        if not isinstance(states, torch.Tensor) or not states.is_contiguous() or states.dtype != self.dtype:
-            raise ValueError(f"states must be a contiguous {'int32' if self.elem32 else 'int64'} tensor")
+        t = self._check_hashing(needs_parameters=True)
+        self._check_layout(states, "states")
         if states.numel() == 0 or states.numel() % t:
             raise ValueError(f"states must hold a positive multiple of {t} elements, not {states.numel()}")
-        self._check_matrix_device(states, "states")
-        _L.check(self._lib.ntt_poseidon2_permute(self._h, C.c_void_p(states.data_ptr()), states.numel() // t,
+        self._check_device((states, "states"))
+        _L.check(self._lib.ntt_poseidon2_permute(self._h, _ptr(states), states.numel() // t,
                                                  _stream_ptr(stream, states.device)), "ntt_poseidon2_permute")
         return states
 
@@ -652,14 +619,13 @@ class NTTPlan:
         [N][width] (ntt_merkle_commit): the leaf digests first, in row order, the root last."""
         log_rows = self._check_hash_call(width, log_rows)
         rows, d = 1 << log_rows, self.poseidon2_width // 2
-        self._check_deep_matrix(mat, rows, width)
+        self._check_matrix(mat, rows, width, "mat", log_rows)
         self._check_matrix(tree, 2 * rows - 1, d, "tree")
         eb = self.elem_bytes
         self._check_no_overlap(tree, "tree", (2 * rows - 1) * d * eb, ((mat, "mat", rows * width * eb),))
-        for t, what in ((mat, "mat"), (tree, "tree")):
-            self._check_matrix_device(t, what)
-        _L.check(self._lib.ntt_merkle_commit(self._h, C.c_void_p(mat.data_ptr()), int(width), int(log_rows),
-                                             C.c_void_p(tree.data_ptr()), _stream_ptr(stream, tree.device)),
+        self._check_device((mat, "mat"), (tree, "tree"))
+        _L.check(self._lib.ntt_merkle_commit(self._h, _ptr(mat), int(width), int(log_rows),
+                                             _ptr(tree), _stream_ptr(stream, tree.device)),
                  "ntt_merkle_commit")
         return tree
 
@@ -681,16 +647,14 @@ class NTTPlan:
         eb = self.elem_bytes
         inputs = [(tree, "tree", (2 * rows - 1) * d * eb), (index, "index", nq * 4)]
         if mat is not None:
-            self._check_deep_matrix(mat, rows, width)
+            self._check_matrix(mat, rows, width, "mat", log_rows)
             self._check_matrix(rows_out, nq, width, "rows_out")
             inputs.append((mat, "mat", rows * width * eb))
             self._check_no_overlap(rows_out, "rows_out", nq * width * eb, inputs)
         if paths is not None and log_rows:
             self._check_no_overlap(paths, "paths", nq * log_rows * d * eb, inputs)
-        for t, what in ((mat, "mat"), (tree, "tree"), (index, "index"), (rows_out, "rows_out"), (paths, "paths")):
-            if t is not None:
-                self._check_matrix_device(t, what)
-        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        self._check_device((mat, "mat"), (tree, "tree"), (index, "index"), (rows_out, "rows_out"), (paths, "paths"))
+        ptr = lambda t: None if t is None or t.numel() == 0 else _ptr(t)
         _L.check(self._lib.ntt_merkle_open(self._h, ptr(mat), int(width), int(log_rows), ptr(tree), ptr(index), nq,
                                            ptr(rows_out), ptr(paths), _stream_ptr(stream, tree.device)),
                  "ntt_merkle_open")
@@ -699,14 +663,8 @@ class NTTPlan:
     def merkle_info(self, width: int, *, log_rows: Optional[int] = None):
         """(digest_elems, tree_elems, launches, tail_log) of ``merkle_commit`` at this shape (ntt_merkle_info)."""
         self._check_hashing()
-        if log_rows is None:
-            log_rows = self.log_n
-        if not self._is_int(log_rows) or not 0 <= log_rows <= self.log_n:
-            raise ValueError(f"log_rows must be an integer in [0, {self.log_n}], not {log_rows!r}")
-        if not self._is_int(width) or width < 1:
-            raise ValueError(f"width must be a positive integer, not {width!r}")
-        if (width << log_rows) >= 1 << 32:
-            raise ValueError(f"2^log_rows * width must stay below 2^32, not {1 << log_rows} * {width}")
+        log_rows = self._check_log_rows(log_rows)
+        self._check_shape(width, log_rows)
         d, te, la, tl = C.c_uint(), C.c_uint64(), C.c_uint(), C.c_uint()
         _L.check(self._lib.ntt_merkle_info(self._h, int(width), int(log_rows), C.byref(d), C.byref(te), C.byref(la),
                                            C.byref(tl)), "ntt_merkle_info")
@@ -717,31 +675,15 @@ class NTTPlan:
         if not self.poseidon2_width:  # the engines of the matrix calls
             raise ValueError("batch_inverse and matrix_scan need a Goldilocks plan or a plan of 4-byte elements")
 
-    def _check_ext(self, ext_degree, ext_w, reads_w=True) -> None:
-        if not self._is_int(ext_degree) or ext_degree not in (1, 2, 4):
-            raise ValueError(f"ext_degree must be 1, 2 or 4, not {ext_degree!r}")
-        if reads_w and ext_degree > 1 and (not self._is_int(ext_w) or not 0 < ext_w < self.p):
-            raise ValueError(f"ext_w must be a canonical nonzero integer (0 < ext_w < p), not {ext_w!r}")
-
-    def _check_flat(self, t, name) -> None:
-        if not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.dtype != self.dtype:
-            raise ValueError(f"{name} must be a contiguous {'int32' if self.elem32 else 'int64'} tensor in the plan's "
-                             "element layout")
-
-    def _check_same_or_apart(self, a, a_name, b, b_name, nbytes) -> None:
-        a0, b0 = a.data_ptr(), b.data_ptr()
-        if a0 != b0 and a0 < b0 + nbytes and b0 < a0 + nbytes:
-            raise ValueError(f"{a_name} and {b_name} overlap (they may be the same buffer, or apart)")
-
     def batch_inverse(self, t: torch.Tensor, out: Optional[torch.Tensor] = None, *, ext_degree: int = 1, ext_w: int = 0,
                       stream=None) -> torch.Tensor:
         """``out`` = [count][ext_degree] receives the inverse of every element of ``t`` in the plan's I/O form
         (ntt_batch_inverse); a zero element gives zero.  ``out`` None: in place."""
         self._check_scan_engine()
         self._check_ext(ext_degree, ext_w)
-        self._check_flat(t, "t")
+        self._check_layout(t, "t")
         out = t if out is None else out
-        self._check_flat(out, "out")
+        self._check_layout(out, "out")
         elems = t.numel() * t.element_size() // self.elem_bytes
         if elems == 0 or elems % ext_degree:
             raise ValueError(f"t must hold a positive multiple of {ext_degree} elements, not {elems}")
@@ -749,10 +691,9 @@ class NTTPlan:
             raise ValueError(f"count * ext_degree must stay below 2^32, not {elems}")
         if out.numel() != t.numel():
             raise ValueError(f"out: expected {t.numel()} elements like t, not {out.numel()}")
-        self._check_same_or_apart(t, "t", out, "out", elems * self.elem_bytes)
-        for x, what in ((t, "t"), (out, "out")):
-            self._check_matrix_device(x, what)
-        _L.check(self._lib.ntt_batch_inverse(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(out.data_ptr()),
+        self._check_no_overlap(out, "out", elems * self.elem_bytes, ((t, "t", elems * self.elem_bytes),), same_ok=True)
+        self._check_device((t, "t"), (out, "out"))
+        _L.check(self._lib.ntt_batch_inverse(self._h, _ptr(t), _ptr(out),
                                              elems // ext_degree, int(ext_degree), int(ext_w) if ext_degree > 1 else 0,
                                              _stream_ptr(stream, out.device)), "ntt_batch_inverse")
         return out
@@ -763,9 +704,9 @@ class NTTPlan:
         if op not in ("sum", "product"):
             raise ValueError(f"op must be 'sum' or 'product', not {op!r}")
         self._check_ext(ext_degree, ext_w, reads_w=op == "product")
-        if not self._is_int(width) or width < 1:
+        if not _is_int(width) or width < 1:
             raise ValueError(f"width must be a positive integer, not {width!r}")
-        if not self._is_int(rows) or rows < 1:
+        if not _is_int(rows) or rows < 1:
             raise ValueError(f"rows must be a positive integer, not {rows!r}")
         if rows * width * ext_degree >= 1 << 32:
             raise ValueError(f"rows * width * ext_degree must stay below 2^32, not {rows} * {width} * {ext_degree}")
@@ -778,31 +719,29 @@ class NTTPlan:
         (``exclusive``: r < i, row 0 the identity) for ``mat`` = [rows][width] elements of ``ext_degree`` coefficients
         (ntt_matrix_scan); ``totals`` = [width][ext_degree] receives the columns' totals.  ``out`` may be ``mat``.
         ``rows`` defaults to what ``mat`` holds."""
-        self._check_flat(mat, "mat")
-        if rows is None and self._is_int(width) and width > 0 and self._is_int(ext_degree) and ext_degree in (1, 2, 4):
+        self._check_layout(mat, "mat")
+        if rows is None and _is_int(width) and width > 0 and _is_int(ext_degree) and ext_degree in (1, 2, 4):
             rows = mat.numel() * mat.element_size() // (self.elem_bytes * width * ext_degree)
         opn = self._check_scan_shape(width, ext_degree, ext_w, op, rows)
         if not isinstance(exclusive, bool):
             raise ValueError(f"exclusive must be a bool, not {exclusive!r}")
-        self._check_flat(out, "out")
+        self._check_layout(out, "out")
         elems = rows * width * ext_degree
         for x, what in ((mat, "mat"), (out, "out")):
             if x.numel() * x.element_size() != elems * self.elem_bytes:
                 raise ValueError(f"{what}: expected {rows} rows of {width * ext_degree} elements of {self.elem_bytes} bytes")
-        self._check_same_or_apart(mat, "mat", out, "out", elems * self.elem_bytes)
+        self._check_no_overlap(out, "out", elems * self.elem_bytes, ((mat, "mat", elems * self.elem_bytes),), same_ok=True)
         if totals is not None:
-            self._check_flat(totals, "totals")
+            self._check_layout(totals, "totals")
             if totals.numel() * totals.element_size() != width * ext_degree * self.elem_bytes:
                 raise ValueError(f"totals: expected {width} rows of {ext_degree} elements of {self.elem_bytes} bytes")
             self._check_no_overlap(totals, "totals", width * ext_degree * self.elem_bytes,
                                    ((mat, "mat", elems * self.elem_bytes), (out, "out", elems * self.elem_bytes)))
-        for x, what in ((mat, "mat"), (out, "out"), (totals, "totals")):
-            if x is not None:
-                self._check_matrix_device(x, what)
-        _L.check(self._lib.ntt_matrix_scan(self._h, C.c_void_p(mat.data_ptr()), C.c_void_p(out.data_ptr()), int(rows),
+        self._check_device((mat, "mat"), (out, "out"), (totals, "totals"))
+        _L.check(self._lib.ntt_matrix_scan(self._h, _ptr(mat), _ptr(out), int(rows),
                                            int(width), int(ext_degree), int(ext_w) if ext_degree > 1 and opn else 0, opn,
                                            _L.NTT_SCAN_EXCLUSIVE if exclusive else 0,
-                                           None if totals is None else C.c_void_p(totals.data_ptr()),
+                                           None if totals is None else _ptr(totals),
                                            _stream_ptr(stream, out.device)), "ntt_matrix_scan")
         return out
 
@@ -827,16 +766,16 @@ class NTTPlan:
     def pointwise_mul(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, stream=None) -> torch.Tensor:
         for t in (a, b, out):
             self._check_tensor(t)
-        _L.check(self._lib.ntt_pointwise_mul(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                             C.c_void_p(out.data_ptr()), _stream_ptr(stream, a.device)),
+        _L.check(self._lib.ntt_pointwise_mul(self._h, _ptr(a), _ptr(b),
+                                             _ptr(out), _stream_ptr(stream, a.device)),
                  "ntt_pointwise_mul")
         return out
 
     def polymul(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, stream=None) -> torch.Tensor:
         for t in (a, b, out):
             self._check_tensor(t)
-        _L.check(self._lib.ntt_polymul(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                       C.c_void_p(out.data_ptr()), _stream_ptr(stream, a.device)), "ntt_polymul")
+        _L.check(self._lib.ntt_polymul(self._h, _ptr(a), _ptr(b),
+                                       _ptr(out), _stream_ptr(stream, a.device)), "ntt_polymul")
         return out
 
     def inverse_pointwise_batch(self, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, batch: int,
@@ -844,8 +783,8 @@ class NTTPlan:
         """out = INTT(a * b) over `batch` transforms (a, b already forward-transformed)."""
         for t in (a, b, out):
             self._check_tensor(t, batch)
-        _L.check(self._lib.ntt_inverse_pointwise_batch(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                                       C.c_void_p(out.data_ptr()), int(batch),
+        _L.check(self._lib.ntt_inverse_pointwise_batch(self._h, _ptr(a), _ptr(b),
+                                                       _ptr(out), int(batch),
                                                        _stream_ptr(stream, a.device)), "ntt_inverse_pointwise_batch")
         return out
 
@@ -853,7 +792,7 @@ class NTTPlan:
         """SURVEY §8d synthetic inputs on the device: 'iota' (x_j = j) or 'random' (SplitMix64)."""
         self._check_tensor(t)
         k = {"iota": 0, "random": 1}[kind]
-        _L.check(self._lib.ntt_fill(self._h, C.c_void_p(t.data_ptr()), k, int(seed), _stream_ptr(stream, t.device)),
+        _L.check(self._lib.ntt_fill(self._h, _ptr(t), k, int(seed), _stream_ptr(stream, t.device)),
                  "ntt_fill")
         return t
 
@@ -862,7 +801,7 @@ class NTTPlan:
         """Local element i <- synthetic value of global j = row0 + (i >> log_inner) + ((i & m) << log_stride)."""
         count = t.numel() * t.element_size() // self.elem_bytes
         k = {"iota": 0, "random": 1}[kind]
-        _L.check(self._lib.ntt_fill_map(self._h, C.c_void_p(t.data_ptr()), count, k, int(seed), int(row0),
+        _L.check(self._lib.ntt_fill_map(self._h, _ptr(t), count, k, int(seed), int(row0),
                                         int(log_inner), int(log_stride), _stream_ptr(stream, t.device)),
                  "ntt_fill_map")
         return t
@@ -872,7 +811,7 @@ class NTTPlan:
         """dst[q * peer_stride + a * bw + b % bw] = src[a][b] * w_n^(+-(row0 + a) * b), q = b >> log_block
         (four-step twiddle + pack; peer_stride defaults to the dense 2^(log_rows + log_block))."""
         ps = (1 << (log_rows + log_block)) if peer_stride is None else int(peer_stride)
-        _L.check(self._lib.ntt_twiddle_pack_ex(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+        _L.check(self._lib.ntt_twiddle_pack_ex(self._h, _ptr(src), _ptr(dst),
                                                int(log_rows), int(log_row_len), int(log_block), int(row0),
                                                int(bool(inverse)), ps, _stream_ptr(stream, src.device)),
                  "ntt_twiddle_pack_ex")
@@ -884,7 +823,7 @@ class NTTPlan:
         block_stride elements (default: one dense [rows][cols] matrix)."""
         lb = log_rows if log_block_rows is None else int(log_block_rows)
         bs = (1 << (lb + log_cols)) if block_stride is None else int(block_stride)
-        _L.check(self._lib.ntt_transpose_ex(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+        _L.check(self._lib.ntt_transpose_ex(self._h, _ptr(src), _ptr(dst),
                                             int(log_rows), int(log_cols), lb, bs, _stream_ptr(stream, src.device)),
                  "ntt_transpose_ex")
         return dst
@@ -968,7 +907,7 @@ def SSIP(x: torch.Tensor, omega: int = 3, log_n: Optional[int] = None) -> torch.
     if x.dtype != torch.int64 or not x.is_cuda or x.numel() != (1 << log_n):
         raise ValueError("SSIP expects a device int64 tensor of 2^log_n elements")
     with torch.cuda.device(x.device):
-        lib.SSIP(C.c_void_p(x.data_ptr()), int(omega), int(log_n))
+        lib.SSIP(_ptr(x), int(omega), int(log_n))
     _L.check(lib.ntt_last_error(), "SSIP")
     return x
 
@@ -982,6 +921,6 @@ def NTT_GZKP(data: torch.Tensor, length: int, prime: int, omega: int, B: int = 5
     p32 = (C.c_uint32 * 8)(*[(prime >> (32 * i)) & 0xFFFFFFFF for i in range(8)])
     g32 = (C.c_uint32 * 8)(*[(omega >> (32 * i)) & 0xFFFFFFFF for i in range(8)])
     with torch.cuda.device(data.device):
-        st = lib.NTT_GZKP_256(C.c_void_p(data.data_ptr()), int(length), None, 0, p32, g32, int(B), int(G))
+        st = lib.NTT_GZKP_256(_ptr(data), int(length), None, 0, p32, g32, int(B), int(G))
     _L.check(st, "NTT_GZKP")
     return data

@@ -282,6 +282,38 @@ def test_the_library_refuses_what_the_python_layer_would():
 
 
 # ------------------------------------------------------------------------------------------------ the pipeline
+def test_29_bit_engines_refuse_the_calls():
+    """A plan of another engine answers NTT_ERR_ARG to every hashing call, writes no byte of any buffer and leaves
+    the info call's outputs as they were."""
+    import ctypes as C
+    from ntt_amd import lib as Lb
+    from ntt_amd.ntt import NTTPlan
+    so = Lb.load()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    u64 = lambda vals: (C.c_uint64 * len(vals))(*vals)
+    width, rows, nq, t, rf, rp = 5, 64, 3, 16, 8, 13  # well-formed arguments for the 4-byte fields' width 16
+    ext_rc, int_rc, int_diag = u64(range(1, rf * t + 1)), u64(range(1, rp + 1)), u64(range(2, t + 2))
+    for pl, words in ((NTTPlan(1, 10, 4), 4), (NTTPlan(0, 10, 1), 1)):  # BN254, P469762049
+        assert so.ntt_plan_set_poseidon2(pl._h, t, 7, rf, rp, ext_rc, int_rc, int_diag) == Lb.NTT_ERR_ARG
+        sizes = {"states": 4 * t, "mat": rows * width, "tree": (2 * rows - 1) * (t // 2), "rows": nq * width,
+                 "paths": nq * 6 * (t // 2)}
+        buf = {k: torch.full((n * words,), 1 + i, dtype=torch.int64, device="cuda:0") for i, (k, n) in enumerate(sizes.items())}
+        index = torch.tensor([0, 5, 63], dtype=torch.int32, device="cuda:0")
+        keep = {k: x.clone() for k, x in buf.items()}
+        ptr = {k: C.c_void_p(x.data_ptr()) for k, x in buf.items()}
+        assert so.ntt_poseidon2_permute(pl._h, ptr["states"], 4, st) == Lb.NTT_ERR_ARG
+        assert so.ntt_merkle_commit(pl._h, ptr["mat"], width, 6, ptr["tree"], st) == Lb.NTT_ERR_ARG
+        assert so.ntt_merkle_open(pl._h, ptr["mat"], width, 6, ptr["tree"], C.c_void_p(index.data_ptr()), nq, ptr["rows"],
+                                  ptr["paths"], st) == Lb.NTT_ERR_ARG
+        d, te, la, tl = C.c_uint(77), C.c_uint64(78), C.c_uint(79), C.c_uint(80)
+        assert so.ntt_merkle_info(pl._h, width, 6, C.byref(d), C.byref(te), C.byref(la), C.byref(tl)) == Lb.NTT_ERR_ARG
+        assert (d.value, te.value, la.value, tl.value) == (77, 78, 79, 80)
+        torch.cuda.synchronize()
+        for k, x in buf.items():
+            assert torch.equal(x, keep[k]), k
+        assert index.tolist() == [0, 5, 63]
+
+
 @pytest.mark.parametrize("fid,d,w", [(4, 4, 11), (3, 2, 7)])
 def test_pipeline_extension_commit_fold_commit(fid, d, w):
     """lde_matrix(bitrev_out) -> commit; fri_fold -> commit of the [M >> k][d << k] view: both roots against the
