@@ -248,29 +248,129 @@ def _inverse(pl, x, d, w, in_place=False, off=0):
     return T._host(out, x.shape[0], d)
 
 
+INV_FORMS = (None, 0, 1, 2)  # NTT_INV_FORM unset (the default form, 1) and every form by name
+
+
+def _set_form(monkeypatch, form):
+    """NTT_INV_FORM is read at every ntt_batch_inverse call: setting it in this process is enough."""
+    if form is None:
+        monkeypatch.delenv("NTT_INV_FORM", raising=False)
+    else:
+        monkeypatch.setenv("NTT_INV_FORM", str(form))
+
+
+def _inv_run(pl, d, form):
+    """A thread's run of elements at this form: InvShape::run_words(form) / (words per element * d), 32 words at
+    form 1 (and unset), 16 at forms 0 and 2 (scan_shape.hpp)."""
+    return (32 if form in (None, 1) else 16) // (pl.elem_bytes // 4 * d)
+
+
+def _inv_counts(run):
+    """1, 2, around a thread's run, around one wave's span (64 runs), a workgroup's worth + 1 (a second workgroup
+    that holds one element) and + 3, 2^16 + 7."""
+    return sorted({1, 2, run - 1, run, run + 1, 64 * run - 1, 64 * run, 64 * run + 1, 256 * run + 1, 256 * run + 3,
+                   (1 << 16) + 7} - {0})
+
+
+def _inv_input(p, count, run, d):
+    """Seeded values with 1 and p - 1 and, where the count allows, the zero patterns: by thread run (the first
+    position of the second run, the last of the third, a whole run) and by wave of 64 runs (lane 63's last element
+    in wave 0, lane 0's first in wave 1, one whole lane of the otherwise non-zero wave 2, all of wave 3 beside the
+    untouched wave 4, all of wave 5 but one element); for d > 1 an element whose coordinate 0 alone is zero, beside
+    a zero element.  Returns (x, the positions to check element by element)."""
+    x = _data(p, count, d, 20 + count % 97)
+    x[count // 3] = 1
+    x[count // 3, 1:] = 0
+    x[count // 2] = p - 1
+    wave = 64 * run
+    if count > 4 * run:
+        x[run] = 0                      # the first position of the second run
+        x[3 * run - 1] = 0              # the last position of the third
+        x[4 * run:5 * run] = 0          # a whole run
+    if count >= wave:
+        x[wave - 1] = 0                 # lane 63's last element
+    if count > wave:
+        x[wave] = 0                     # lane 0's first element of the next wave
+    if count >= 3 * wave:
+        lo = 2 * wave
+        x[lo:lo + wave][~x[lo:lo + wave].any(axis=1)] = 3   # wave 2: nothing zero ...
+        x[lo + 17 * run:lo + 18 * run] = 0                  # ... but lane 17's whole run
+    if count >= 4 * wave:
+        x[3 * wave:4 * wave] = 0        # every element of wave 3
+        hi = min(count, 5 * wave)
+        x[4 * wave:hi][~x[4 * wave:hi].any(axis=1)] = 3     # wave 4 (what the count has of it): nothing zero
+    one = None
+    if count >= 6 * wave:
+        one = 5 * wave + 31 * run + min(1, run - 1)
+        keep = x[one].copy()
+        x[5 * wave:6 * wave] = 0        # wave 5: every element but one
+        x[one] = keep if keep.any() else 3
+    c0 = None
+    if d > 1 and count >= 2:            # zero in coordinate 0 only: invertible
+        c0 = wave + 1 if count > wave + 1 else (5 * run if count > 5 * run else count - 1)  # on no zero's place
+        x[c0] = 5
+        x[c0, 0] = 0
+    zero = ~x.any(axis=1)
+    edges = np.flatnonzero(zero[1:] != zero[:-1])  # a zero beside a non-zero: both sides
+    pos = {0, count - 1} | {int(e) for e in edges} | {int(e) + 1 for e in edges}
+    pos |= {q for q in (7, 8, 9, count // 3, count // 2, one, c0) if q is not None and q < count}
+    if c0 is not None:
+        pos |= {c0 - 1} | ({c0 + 1} if c0 + 1 < count else set())
+    pos |= {int(q) for q in np.linspace(0, count - 1, 16).astype(np.int64)}  # at least 16 where the count has them
+    assert len(pos) >= min(count, 16)
+    return x, sorted(pos)
+
+
+def _from_io(y, pl):
+    """The plan's I/O form -> canonical values."""
+    if not pl.montgomery_io:
+        return y
+    return (y.astype(object) * pow(1 << 32, -1, pl.p) % pl.p).astype(np.uint64)
+
+
+def _inverse_sweep(pl, fid, d, w, form):
+    """Every count and zero pattern of this form's run, in the three buffer forms: in * out = 1 and 0 -> 0 on all
+    elements (is_inverse), and the oracle's own inverse element by element at the chosen positions."""
+    p, _ = T._params(fid)
+    run = _inv_run(pl, d, form)
+    for count in _inv_counts(run):
+        x, pos = _inv_input(p, count, run, d)
+        want = {q: R.ext_inverse([int(v) for v in x[q]], w, p) for q in pos}
+        for kw in ({}, {"in_place": True}, {"off": 1}):
+            got = _from_io(_inverse(pl, D._to_io(x, pl), d, w, **kw), pl)
+            assert R.is_inverse(x, got, d, w, p), (fid, d, form, count, kw)
+            bad = [q for q in pos if [int(v) for v in got[q]] != want[q]]
+            assert not bad, (fid, d, form, count, kw, bad[:8])
+    return x, got
+
+
+@pytest.mark.parametrize("form", INV_FORMS)
 @pytest.mark.parametrize("fid,d,w", EXTS)
-def test_batch_inverse(fid, d, w):
-    """in * out = 1 through the oracle's product and 0 -> 0 exactly: counts 1, 2, around a thread's run, a
-    workgroup's worth + 3 and 2^16 + 7; random values, 1 and p - 1, a zero at the first and last position of a run
-    and a whole run of zeros; in place and one element past a 16-byte boundary."""
+def test_batch_inverse(fid, d, w, form, monkeypatch):
+    """in * out = 1 through the oracle's product and 0 -> 0 exactly, at every NTT_INV_FORM (unset too), the run taken
+    from the form: counts 1, 2, around a thread's run, around a wave's span, a workgroup's worth + 1 and + 3 and
+    2^16 + 7; random values, 1 and p - 1, a zero at the first and last position of a run and a whole run of zeros,
+    the zero patterns by wave of _inv_input; in place and one element past a 16-byte boundary.  Bit-exact against
+    tests/scan_ref.py alone: nothing is compared between forms."""
+    _set_form(monkeypatch, form)
     p, _ = T._params(fid)
     pl = T._plan(fid, LOG_N)
-    run = (32 if pl.elem32 else 16) // d  # a thread's run: 32 words of 4-byte, 16 of 8-byte elements (ntt.h)
-    for count in sorted({1, 2, run - 1, run, run + 1, 256 * run + 3, (1 << 16) + 7} - {0}):
-        x = _data(p, count, d, 20 + count % 97)
-        x[count // 3] = 1
-        x[count // 3, 1:] = 0
-        x[count // 2] = p - 1
-        if count > 4 * run:
-            x[run] = 0                      # the first position of the second run
-            x[3 * run - 1] = 0              # the last position of the third
-            x[4 * run:5 * run] = 0          # a whole run
-        for kw in ({}, {"in_place": True}, {"off": 1}):
-            got = _inverse(pl, x, d, w, **kw)
-            assert R.is_inverse(x, got, d, w, p), (fid, d, count, kw)
+    assert _inv_run(pl, d, None) == (32 if pl.elem32 else 16) // d  # 32 words of 4-byte, 16 of 8-byte elements (ntt.h)
+    x, got = _inverse_sweep(pl, fid, d, w, form)
     for k in range(3):  # against the oracle's own inverse, element by element
         a = [int(v) for v in x[k + 7]]
         assert [int(v) for v in got[k + 7]] == R.ext_inverse(a, w, p)
+
+
+@pytest.mark.parametrize("form", (0, 2))
+def test_inverse_forms_on_the_montgomery_plan(form, monkeypatch):
+    """The same sweep at forms 0 and 2 on BabyBear with NTT_PLAN_MONTGOMERY_IO (test_montgomery_plan_keeps_the_form
+    runs form 1): Montgomery-form data in and out."""
+    _set_form(monkeypatch, form)
+    fid, d, w = 4, 4, 11
+    pl = T._plan(fid, LOG_N, montgomery_io=True)
+    _inverse_sweep(pl, fid, d, w, form)
+    assert pl.device_status() == 0
 
 
 # ------------------------------------------------------------------------------------------------ pipeline
@@ -373,6 +473,7 @@ def test_29_bit_engines_refuse_the_calls():
 
 
 CHILD = r'''
+import os
 import sys
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -393,6 +494,12 @@ for fid, d, w in ((3, 2, 7), (4, 4, 11)):
     assert R.is_inverse(x, S._inverse(pl, x, d, w), d, w, p)
     st = pl.device_status()
     assert st == 0, (fid, hex(st))
+    for form in (0, 2):  # NTT_INV_FORM is read at every call
+        os.environ["NTT_INV_FORM"] = str(form)
+        S._inverse_sweep(pl, fid, d, w, form)
+        st = pl.device_status()
+        assert st == 0, (fid, form, hex(st))
+    del os.environ["NTT_INV_FORM"]
     bad = S._data(p, 100, d, 6)
     bad[37, d - 1] = p  # one non-canonical element
     S._scan(pl, bad, 1, d, w, "product", False)
@@ -408,7 +515,8 @@ print("SCAN-DEBUG-OK")
 
 def test_checked_build_reports_clean_status():
     """Scans of both layouts and an inverse on both engines through the checked build in a fresh process: right
-    results and no bounds / canonical report; an input with one element equal to p reports 0x200."""
+    results and no bounds / canonical report, the inverse's sweep at forms 0 and 2 included; an input with one element
+    equal to p reports 0x200."""
     env = dict(os.environ, NTT_LIB_PATH=DEBUG_LIB)
     r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + CHILD], env=env, capture_output=True, text=True,
                        timeout=240)
